@@ -16,7 +16,10 @@ Contract: python bench.py --gpus N --steps K --warmup W
   the only exchange is the packed-tensor merge (merge.distributed_merge:
   32 B top-K records allgather + dense-bucket sum-reduce + sideband bytes,
   no pickled objects).
-Rank 0 prints ONE JSON line with metric/value plus:
+Rank 0 prints ONE JSON line with metric/value/ms_per_step. A plain run does
+only what that headline needs: set up, warm up, time the K steps, write the
+outputs when --dump-outputs is given, print the line (roofline and
+cpu_baseline are null). --full adds the secondary measurements:
   roofline: dominant kernel algorithmic-bytes/launch over its HIP-event
     launch time, vs 8 TB/s HBM3E peak (MI355X_MICROARCH.md). Algorithmic
     bytes are counted from the generated index, not from DRAM
@@ -24,6 +27,13 @@ Rank 0 prints ONE JSON line with metric/value plus:
   cpu_baseline: the oracle (reference restatement, kind "port") timed on this
     box's host cores on a bounded sample (--cpu-baseline-docs), repeated
     until >=2 s of wall time so the rate is honestly measurable.
+
+--dump-outputs DIR writes what the last timed step returned (the decoded
+LeafSearchResponse a caller receives: counts, top-K hits, finalized
+aggregations) as DIR/<name>.npy float64 arrays, all finite: an optional
+value comes with a <name>_state array (1 value, 0 absent). Inputs are
+seeded, so two builds run with the same arguments can be compared output
+for output.
 
 Extra workloads (NOT the default the driver runs):
   --workload range    bool must severity_text:INFO + u64 tenant_id range
@@ -34,10 +44,12 @@ Extra workloads (NOT the default the driver runs):
 """
 import argparse
 import json
+import math
 import os
 import sys
 import tempfile
 import time
+import zlib
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
@@ -175,6 +187,81 @@ def cached_split(rank, docs, seed=42):
     return data
 
 
+def _finite(x):
+    """-> (value, state). Every dumped number is finite: a value the response
+    does not carry (state 0) or a non-finite one (2 nan, 3 +inf, 4 -inf) is
+    written as 0.0 and told apart by its state; 1 = ordinary value."""
+    if x is None:
+        return 0.0, 0.0
+    x = float(x)
+    if math.isfinite(x):
+        return x, 1.0
+    return 0.0, 2.0 if math.isnan(x) else 3.0 if x > 0 else 4.0
+
+
+def _sort_value(sv):
+    """SortByValue oneof -> number (None when the hit carries none)."""
+    for k in ("f64", "u64", "i64", "boolean"):
+        if sv and k in sv:
+            return sv[k]
+    return None
+
+
+def _flatten_numbers(node, out):
+    """Leaves of a finalized aggregation JSON in a fixed order (dict keys
+    sorted, lists in order); string keys enter as their CRC32 so bucket
+    identity is compared too, null metrics stay null."""
+    if isinstance(node, dict):
+        for k in sorted(node):
+            _flatten_numbers(node[k], out)
+    elif isinstance(node, list):
+        for v in node:
+            _flatten_numbers(v, out)
+    elif isinstance(node, str):
+        out.append(zlib.crc32(node.encode()))
+    else:
+        out.append(node)
+
+
+def dump_outputs(out_dir, resp, searcher, aggregation):
+    """Write the last timed step's response as float64 .npy arrays (a few KB:
+    top-K hits and finalized buckets, never per-doc data). Timings
+    (resource_stats) are not outputs and stay out. Optional values come as
+    a <name> / <name>_state pair (_finite)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    hits = resp.get("partial_hits", [])
+    arrays = {
+        "counts": [resp.get("num_hits", 0),
+                   resp.get("num_attempted_splits", 0),
+                   resp.get("num_successful_splits", 0),
+                   len(resp.get("failed_splits", []))],
+        "hit_doc_id": [h.get("doc_id", 0) for h in hits],
+        "hit_segment_ord": [h.get("segment_ord", 0) for h in hits],
+        # split ids are synthetic-<seed>-<ordinal>
+        "hit_split_ord": [int(h["split_id"].rsplit("-", 1)[1]) for h in hits],
+    }
+    optional = {
+        "hit_sort_value": [_sort_value(h.get("sort_value")) for h in hits],
+        "hit_sort_value2": [_sort_value(h.get("sort_value2")) for h in hits],
+    }
+    blob = resp.get("intermediate_aggregation_result")
+    if aggregation and blob:
+        flat = []
+        _flatten_numbers(searcher.finalize_agg_json(blob, aggregation), flat)
+        optional["agg_values"] = flat
+    for name, vals in optional.items():
+        pairs = [_finite(v) for v in vals]
+        arrays[name] = [v for v, _ in pairs]
+        arrays[name + "_state"] = [st for _, st in pairs]
+    for name, vals in arrays.items():
+        arr = np.asarray(vals, dtype=np.float64)
+        if arr.size == 0:
+            continue  # no hits requested: counts.npy already says so
+        assert np.isfinite(arr).all(), name
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -190,6 +277,13 @@ def main():
                     help="splits per GPU (docs are divided across them); "
                          "config5's 1-GPU slice is --docs 125000000 "
                          "--splits 8")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as "
+                         "DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also compute the roofline figure and time the CPU "
+                         "baseline (off by default: a plain run measures "
+                         "the headline only)")
     ap.add_argument("--cpu-baseline-steps", type=int, default=2)
     ap.add_argument("--cpu-baseline-docs", type=int, default=0,
                     help="oracle sample size (0 = min(docs, 10M))")
@@ -297,9 +391,12 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     p50_ms = sorted(step_times)[len(step_times) // 2] * 1e3
 
-    # roofline of the dominant kernel
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, resp, searcher, wl["aggregation"])
+
+    # roofline of the dominant kernel (--full)
     kms, launches = (searcher.kernel_stats(wl["kernel"])
-                     if engine != "oracle" else (0.0, 0))
+                     if args.full and engine != "oracle" else (0.0, 0))
     roofline = None
     if launches:
         ms_per_launch = kms / launches
@@ -319,9 +416,9 @@ def main():
     # (SURVEY §8d): the reference's rayon model is one thread per split, so
     # the sample is sharded into nproc splits and the oracle's OpenMP loop
     # runs one split per core. Bounded sample so the default run finishes in
-    # minutes.
+    # minutes. (--full)
     cpu_baseline = None
-    if world == 1 and args.cpu_baseline_steps > 0:
+    if args.full and world == 1 and args.cpu_baseline_steps > 0:
         ncores = os.cpu_count() or 1
         bdocs = args.cpu_baseline_docs or min(args.docs, 10_000_000)
         per = max(bdocs // ncores, 1)

@@ -233,6 +233,15 @@ inline void plan_fingerprint(const PlanNode& n, std::string& out) {
              (long long)n.hi.ival, (long long)n.minimum_should_match,
              double(n.boost), int(n.ci));
     out += buf;
+    // str bounds live in sval and f64 bounds in fval (ival only truncates
+    // them): two ranges differing there must not share a cached bitmap
+    snprintf(buf, sizeof buf, "%.17g:%.17g:%d%d|", n.lo.fval, n.hi.fval,
+             int(n.lo.from_f64), int(n.hi.from_f64));
+    out += buf;
+    out += n.lo.sval;
+    out += '\x1f';
+    out += n.hi.sval;
+    out += '\x1f';
     for (auto* v : {&n.must, &n.must_not, &n.should, &n.filter, &n.cache_inner}) {
         out += '[';
         for (auto& c : *v) plan_fingerprint(c, out);

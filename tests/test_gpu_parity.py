@@ -1227,7 +1227,8 @@ def test_percentiles_aggs():
             d["lat"] = round(rng.uniform(0.0, 5000.0), 3)
         docs.append(d)
     schema = {"timestamp_field": None, "fields":
-              [{"name": "timestamp", "type": "i64", "fast": True},
+              # datetime: date_histogram rejects any other column type
+              [{"name": "timestamp", "type": "datetime", "fast": True},
                {"name": "severity_text", "type": "text", "tokenizer": "raw",
                 "fast": True},
                {"name": "body", "type": "text"},
