@@ -38,7 +38,7 @@ class _BaseSearcher:
 
     def __init__(self, create_arg=None):
         # QW_PRODUCT_LIB: perf-experiment override for the product library
-        # path (e.g. a -DQW_TILE_DOCS variant built alongside the default)
+        # path (a variant .so built alongside the default)
         override = os.environ.get("QW_PRODUCT_LIB")
         if override and self._libname == "libquickwit_amd.so":
             path = override

@@ -7,8 +7,9 @@
 
 namespace qw {
 
-// docs per workgroup tile — build-time switch (-DQW_TILE_DOCS=4096) so the
-// LDS-footprint/occupancy tradeoff can be measured as whole-library variants
+// docs per workgroup tile. The collection phase of k_leaf_tile_t assumes one
+// 32-doc bitset word per thread (static_assert in kernels.hip), so the only
+// value that compiles is 32 * TILE_THREADS.
 #ifndef QW_TILE_DOCS
 #define QW_TILE_DOCS 8192
 #endif

@@ -1013,6 +1013,11 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
                                       threadIdx.x] = sc_bits_m[threadIdx.x];
         }
         if (NC) {
+            // the bitmap store above, the prefix scan and the emit loop below
+            // all index the match bitset by threadIdx.x: with fewer words than
+            // threads they read past the bitset, with more they drop matches
+            static_assert(TILE_DOCS == 32 * TILE_THREADS,
+                          "collection assumes one 32-doc bitset word per thread");
             __syncthreads();  // bits_m/score final
             uint32_t w = threadIdx.x;  // one 32-doc word per thread (256 words)
             uint32_t cnt = __popc(sc_bits_m[w]);

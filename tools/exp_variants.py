@@ -1,9 +1,8 @@
 """Decode-kernel variant shoot-out (one gpurun call): times the dominant
 kernel of the flagship workloads across library variants x env toggles.
 
-Variants are whole product .so builds (QW_PRODUCT_LIB): the default
-TILE_DOCS=8192 and a -DQW_TILE_DOCS=4096 build; env toggles kill the LDS
-norms/ktab staging so each lever is measured separately. Prints one line
+Variants are whole product .so builds (QW_PRODUCT_LIB); env toggles kill the
+LDS norms/ktab staging so each lever is measured separately. Prints one line
 per (variant, toggles, workload): main-kernel ms/launch + p50 leaf ms.
 """
 import argparse
@@ -60,8 +59,7 @@ def main():
     ap.add_argument("--docs", type=int, default=100_000_000)
     args = ap.parse_args()
 
-    variants = [("t8192", os.path.join(REPO, "libquickwit_amd.so")),
-                ("t4096", os.path.join(REPO, "libqw_t4096.so"))]
+    variants = [("t8192", os.path.join(REPO, "libquickwit_amd.so"))]
     toggles = [("lds_both", {}),
                ("lds_off", {"QW_NO_LDS_NORMS": "1", "QW_NO_LDS_KTAB": "1"}),
                ("lds_ktab_only", {"QW_NO_LDS_NORMS": "1"})]
