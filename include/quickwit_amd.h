@@ -149,6 +149,13 @@ int32_t qw_ctx_memory_stats(qw_ctx* ctx, uint64_t* used_bytes,
 int32_t qw_absence_cache_stats(qw_ctx* ctx, uint64_t* hits, uint64_t* misses,
                                uint64_t* entries);
 
+/* Top-K pruning counters: out[0] = collecting leaf-split calls that ran with
+ * the tile kernel's top-K pruning on, out[1] = those that ran without it
+ * (wide records, K > 64, search_after, or config "topk_prune": false),
+ * out[2] / out[3] = candidate records emitted / docs matched by the last
+ * collecting call. With pruning off the two are equal. */
+int32_t qw_topk_stats(qw_ctx* ctx, uint64_t out[4]);
+
 /* Library version + build arch, e.g. "quickwit_amd 0.1 gfx950". */
 const char* qw_version(void);
 

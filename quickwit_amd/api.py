@@ -197,6 +197,19 @@ class GpuSearcher(_BaseSearcher):
             raise RuntimeError(f"absence_cache_stats failed: {rc}")
         return h.value, m.value, e.value
 
+    def topk_stats(self):
+        """(pruned_calls, unpruned_calls, last_emitted, last_matched): how
+        many collecting leaf-split calls ran with the tile kernel's top-K
+        pruning on / off, and the last one's emitted candidate records and
+        matched docs. Config {"topk_prune": False} turns pruning off."""
+        fn = self._lib.qw_topk_stats
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64 * 4)]
+        out = (ctypes.c_uint64 * 4)()
+        rc = fn(self._ctx, ctypes.byref(out))
+        if rc != 0:
+            raise RuntimeError(f"topk_stats failed: {rc}")
+        return tuple(out)
+
     def device_sync(self):
         self._lib.qw_ctx_device_sync.argtypes = [ctypes.c_void_p]
         rc = self._lib.qw_ctx_device_sync(self._ctx)

@@ -204,6 +204,18 @@ struct QueryDev {
     uint64_t cand_off;         // {u32 key, u32 doc}[cap]
     uint64_t cand_cap;
     uint64_t hist_off;         // u32[TOPK_BINS] histogram of candidate keys
+    // top-K pruning of narrow candidate records (kernels.hip collection
+    // phase): K = max_hits + start_offset when 1 <= K <= 64, else 0 = emit
+    // every match. The running global bound is the u64 at
+    // cand_count_off + TOPK_BOUND_OFF, zeroed with the rest of the header.
+    uint32_t prune_k;
+    uint32_t _pad_prune;
 };
+
+// byte offset of the pruning bound inside the 64-byte cand_count header
+// (u32 words 0..2 are cand_count, the survivors count and the search_after
+// band count)
+constexpr uint32_t TOPK_BOUND_OFF = 16;
+constexpr uint32_t TOPK_PRUNE_MAX_K = 64;
 
 }  // namespace qw

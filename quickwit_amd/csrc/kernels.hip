@@ -82,6 +82,28 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
     return v;
 }
 
+// 64-lane bitonic sort, descending: lane i returns the i-th largest of the
+// wave's values. Shuffles only (21 compare-exchange steps), no LDS, no
+// barrier. tests/test_topk_prune_model.py runs the same network in numpy.
+__device__ __forceinline__ uint64_t wave_sort_desc_u64(uint64_t v) {
+    const uint32_t lane = threadIdx.x & 63u;
+    // rolled on purpose: unrolled, the 21 lane masks are hoisted out of the
+    // tile loop and live in SGPRs across the decode, which spills them
+    #pragma unroll 1
+    for (uint32_t k = 2; k <= 64; k <<= 1) {
+        #pragma unroll 1
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            uint64_t o = (uint64_t(__shfl_xor(uint32_t(v >> 32), int(j), 64)) << 32) |
+                         __shfl_xor(uint32_t(v), int(j), 64);
+            // lower lane of a pair keeps the larger value in a descending
+            // block ((lane & k) == 0; the whole wave at k == 64)
+            bool keep_max = ((lane & j) == 0) == ((lane & k) == 0);
+            v = keep_max ? (v > o ? v : o) : (v < o ? v : o);
+        }
+    }
+    return v;
+}
+
 __device__ __forceinline__ uint32_t f32_sortable(float f) {
     uint32_t b = __float_as_uint(f);
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
@@ -496,7 +518,7 @@ __device__ __forceinline__ int64_t histo_bucket(const QueryDev& q, const AggDev&
 // ---------------------------------------------------------------- main kernel
 // One instantiation per query shape; LDS sections per SmemMap. do_aggs /
 // collect of the old interface became NA / NC.
-template <bool NS, bool NB, bool NA, bool NC>
+template <bool NS, bool NB, bool NA, bool NC, bool PR = false>
 __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
                                                               uint32_t tile_base,
                                                               uint32_t tile_end,
@@ -1012,12 +1034,12 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
             ((uint32_t*)q.bitmap_out)[uint64_t(tile) * (TILE_DOCS / 32) +
                                       threadIdx.x] = sc_bits_m[threadIdx.x];
         }
-        if (NC) {
-            // the bitmap store above, the prefix scan and the emit loop below
-            // all index the match bitset by threadIdx.x: with fewer words than
-            // threads they read past the bitset, with more they drop matches
-            static_assert(TILE_DOCS == 32 * TILE_THREADS,
-                          "collection assumes one 32-doc bitset word per thread");
+        // the bitmap store above, the prefix scan and the emit loop below
+        // all index the match bitset by threadIdx.x: with fewer words than
+        // threads they read past the bitset, with more they drop matches
+        static_assert(TILE_DOCS == 32 * TILE_THREADS,
+                      "collection assumes one 32-doc bitset word per thread");
+        if constexpr (NC && !PR) {
             __syncthreads();  // bits_m/score final
             uint32_t w = threadIdx.x;  // one 32-doc word per thread (256 words)
             uint32_t cnt = __popc(sc_bits_m[w]);
@@ -1063,6 +1085,119 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
                         uint32_t kl = q.sort_asc ? ~d : d;
                         cand[pos] = (uint64_t(kh) << 32) | kl;
                     }
+                }
+            }
+        } else if constexpr (NC) {
+            // PR: the pruned instantiation, launched only for narrow records
+            // with q.prune_k = K in 1..64 (launch_leaf_tile); every other
+            // launch runs the block above, unchanged
+            __syncthreads();  // bits_m/score final
+            uint32_t w = threadIdx.x;  // one 32-doc word per thread (256 words)
+            const uint32_t wbits = sc_bits_m[w];
+            uint32_t cnt = __popc(wbits);
+            uint32_t wv = threadIdx.x >> 6;
+            // narrow record = u64 sort key, larger is better in either
+            // direction; the host truncates to K by plain u64 order
+            auto narrow_key = [&](uint32_t li) -> uint64_t {
+                float sc = (NS && q.scoring) ? sc_score[li] : 0.f;
+                uint32_t d = tile_lo + li;
+                uint32_t kh = q.scoring ? f32_sortable(sc) : 0u;
+                if (q.sort_asc) kh = ~kh;
+                uint32_t kl = q.sort_asc ? ~d : d;
+                return (uint64_t(kh) << 32) | kl;
+            };
+            // ---- top-K pruning (q.prune_k = K): emit
+            // only records whose key reaches a proven lower bound on the
+            // K-th largest key of the whole launch.
+            //   per tile: each word's maximum key (0 = empty word); each
+            //   wave's K-th largest of its 64 word maxima (0 when fewer than
+            //   K words are non-empty); b = the largest of the four. Word
+            //   maxima belong to distinct docs, so >= K docs of this tile
+            //   have key >= b.
+            //   globally: G = running maximum of every tile's b, one u64 in
+            //   the zeroed cand_count header. This tile emits keys >= thr =
+            //   max(G as read, b). Let G* be the final maximum and T* a tile
+            //   that supplied it: T* emits with thr == G*, so its >= K docs
+            //   with key >= G* are written; every other tile has thr <= G*
+            //   and writes everything >= G*. So >= K docs >= G* are written,
+            //   the true K-th key is >= G*, and every top-K doc is written
+            //   whatever order the tiles run in and however stale the value
+            //   of G a tile reads. Relaxed ordering suffices: the value
+            //   carries no dependent data.
+            uint64_t thr;
+            uint32_t ecnt = 0;  // records this word emits
+            {
+                uint64_t wmax = 0;
+                for (uint32_t bits = wbits; bits; bits &= bits - 1u) {
+                    uint64_t key = narrow_key(w * 32u + (__ffs(bits) - 1u));
+                    wmax = key > wmax ? key : wmax;
+                }
+                uint64_t srt = wave_sort_desc_u64(wmax);
+                uint32_t kth_hi = __shfl(uint32_t(srt >> 32), int(q.prune_k - 1), 64);
+                uint32_t kth_lo = __shfl(uint32_t(srt), int(q.prune_k - 1), 64);
+                // sc_word_pref is free until the prefix write below: its
+                // first 10 words carry the four wave bounds and thr
+                if (lane_id() == 0) {
+                    sc_word_pref[2 * wv] = kth_hi;
+                    sc_word_pref[2 * wv + 1] = kth_lo;
+                }
+                __syncthreads();
+                if (threadIdx.x == 0) {
+                    uint64_t b = 0;
+                    for (uint32_t i = 0; i < 4; ++i) {
+                        uint64_t wb = (uint64_t(sc_word_pref[2 * i]) << 32) |
+                                      sc_word_pref[2 * i + 1];
+                        b = wb > b ? wb : b;
+                    }
+                    unsigned long long* g = (unsigned long long*)(
+                        q.results + q.cand_count_off + TOPK_BOUND_OFF);
+                    uint64_t old = atomicMax(g, (unsigned long long)b);
+                    uint64_t t = old > b ? old : b;
+                    sc_word_pref[8] = uint32_t(t >> 32);
+                    sc_word_pref[9] = uint32_t(t);
+                }
+                __syncthreads();
+                thr = (uint64_t(sc_word_pref[8]) << 32) | sc_word_pref[9];
+                if (wmax >= thr)  // else nothing in this word can pass
+                    for (uint32_t bits = wbits; bits; bits &= bits - 1u)
+                        ecnt += narrow_key(w * 32u + (__ffs(bits) - 1u)) >= thr;
+            }
+            // one scan for both counts: matches in the high half (num_hits
+            // comes from tile_counts and must not see the pruning), emitted
+            // records in the low half. A tile holds <= 8192 of either, so
+            // the halves cannot carry into each other.
+            uint32_t packed = (cnt << 16) | ecnt;
+            uint32_t incl = wave_incl_scan_u32(packed);
+            if (lane_id() == 63) sc_wave_base[wv] = incl;
+            __syncthreads();  // also: every thread has read thr
+            uint32_t wave_off = 0;
+            for (uint32_t i = 0; i < wv; ++i) wave_off += sc_wave_base[i];
+            sc_word_pref[w] = (wave_off + incl - packed) & 0xFFFFu;
+            uint32_t tile_total = sc_wave_base[0] + sc_wave_base[1] +
+                                  sc_wave_base[2] + sc_wave_base[3];
+            if (threadIdx.x == 0) {
+                *sc_cand_base = atomicAdd(cand_count, tile_total & 0xFFFFu);
+                if (do_count) tile_counts[tile] = tile_total >> 16;
+            }
+            __syncthreads();
+            uint64_t base = *sc_cand_base;
+            // one 32-doc word per thread, iterating SET bits only (a full
+            // grid-stride re-walk of the tile cost ~as much as the decode
+            // itself at ~25% match density); per-thread writes are
+            // consecutive addresses, coalescing at cache-line granularity
+            if (ecnt) {
+                uint32_t wd = threadIdx.x;
+                uint32_t bits = wbits;
+                uint64_t rank = sc_word_pref[wd];
+                while (bits) {
+                    uint32_t b = __ffs(bits) - 1u;
+                    bits &= bits - 1u;
+                    uint32_t li = wd * 32u + b;
+                    uint64_t key = narrow_key(li);
+                    if (key < thr) continue;
+                    uint64_t pos = base + rank++;
+                    if (pos >= q.cand_cap) break;
+                    cand[pos] = key;
                 }
             }
         } else if (do_count) {
@@ -1120,11 +1255,21 @@ inline uint32_t launch_leaf_tile(bool ns, bool nb, bool na, bool nc, dim3 grid,
     // only for what this query stages
     if (ns && q.norms_stage_off) lds += TILE_DOCS;
     if (ns && q.scoring && q.n_ktabs) lds += 1024 * q.n_ktabs;
+    // top-K pruning has instantiations of its own (collecting shapes only),
+    // so every unpruned launch runs the code it ran before pruning existed
+    const bool pr = q.prune_k != 0;
+    if (pr && (!nc || q.wide_cand || q.prune_k > TOPK_PRUNE_MAX_K))
+        throw std::runtime_error("prune_k needs narrow candidate collection");
     #define QW_CASE(NS_, NB_, NA_, NC_)                                           \
         if (ns == NS_ && nb == NB_ && na == NA_ && nc == NC_) {                   \
-            hipLaunchKernelGGL((k_leaf_tile_t<NS_, NB_, NA_, NC_>), grid,         \
-                               dim3(TILE_THREADS), lds, stream, q, tile_base,     \
-                               tile_end, do_count);                               \
+            if (NC_ && pr)                                                        \
+                hipLaunchKernelGGL((k_leaf_tile_t<NS_, NB_, NA_, NC_, NC_>),      \
+                                   grid, dim3(TILE_THREADS), lds, stream, q,      \
+                                   tile_base, tile_end, do_count);                \
+            else                                                                  \
+                hipLaunchKernelGGL((k_leaf_tile_t<NS_, NB_, NA_, NC_>), grid,     \
+                                   dim3(TILE_THREADS), lds, stream, q, tile_base, \
+                                   tile_end, do_count);                           \
             return lds;                                                           \
         }
     QW_CASE(false, false, false, false)

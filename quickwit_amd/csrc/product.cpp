@@ -345,6 +345,14 @@ struct qw_ctx {
     uint64_t hbm_used = 0;
     uint64_t hbm_budget = 0;
     bool budget_configured = false;
+    // top-K pruning in the tile kernel; config key
+    // "topk_prune" (bool, default true) turns it off for this context, so
+    // one process can hold a pruned and an unpruned searcher. Counters for
+    // qw_topk_stats: collecting leaf calls pruned / unpruned, and the last
+    // collecting call's emitted candidates and matched docs.
+    bool topk_prune = true;
+    uint64_t topk_pruned = 0, topk_unpruned = 0;
+    uint64_t topk_last_emitted = 0, topk_last_matched = 0;
 };
 
 static void qw_check_budget(qw_ctx* ctx, uint64_t need) {
@@ -2013,6 +2021,14 @@ static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
         q.cand_off = r_cand;
         q.cand_cap = cand_cap;
         q.hist_off = r_hist;
+        // prune candidates in the tile kernel: narrow records, small K, no
+        // cursor (the cursor band is cut out of ALL candidates afterwards),
+        // and a real candidate array
+        uint32_t prune_k = 0;
+        if (collect && !wide && !after && cand_cap > 0 && leaf_max_hits >= 1 &&
+            leaf_max_hits <= TOPK_PRUNE_MAX_K && ctx->topk_prune)
+            prune_k = uint32_t(leaf_max_hits);
+        q.prune_k = prune_k;
 
         const char* kname = !fq.terms.empty() ? "union_bm25"
                             : do_aggs         ? "column_agg"
@@ -2069,6 +2085,9 @@ static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
 
         // enqueue top-K histogram pass 0 behind the main kernel (count read
         // device-side) so its result arrives with the same synchronize
+        // (kept when pruning: the 100M flagship still emits ~130k records,
+        // above the 16384 no-refinement threshold, and a pass over that few
+        // costs far less than the extra round trip rerun_select would need)
         bool hist0_valid = false;
         if (collect && !after) {
             uint64_t* d_cand0 = (uint64_t*)(ctx->d_results.p + r_cand);
@@ -2115,6 +2134,11 @@ static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
         HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
         record_kernel_time(ctx, kname, ms);
         for (uint32_t i = 0; i < n_tiles; ++i) matched += tile_counts[i];
+        if (collect) {
+            ++(prune_k ? ctx->topk_pruned : ctx->topk_unpruned);
+            ctx->topk_last_emitted = cand_n;
+            ctx->topk_last_matched = matched;
+        }
 
         // ---- top-K selection over candidates (device histogram refinement
         // + host exact sort of the survivors; top_k_collector.rs semantics)
@@ -2785,6 +2809,9 @@ qw_ctx* qw_ctx_create(const char* config_json) {
                 ctx->hbm_budget = uint64_t(mb->as_i64());
                 ctx->budget_configured = true;
             }
+            if (const mj::Value* tp = cfg->get("topk_prune"))
+                ctx->topk_prune = tp->kind == mj::Value::BOOL ? tp->b
+                                                              : tp->as_i64() != 0;
         }
         return ctx;
     } catch (const std::exception& e) {
@@ -3458,6 +3485,15 @@ int32_t qw_absence_cache_stats(qw_ctx* ctx, uint64_t* hits, uint64_t* misses,
     if (hits) *hits = ctx->absence.hits;
     if (misses) *misses = ctx->absence.misses;
     if (entries) *entries = uint64_t(ctx->absence.keys.size());
+    return QW_OK;
+}
+
+int32_t qw_topk_stats(qw_ctx* ctx, uint64_t out[4]) {
+    if (!ctx || !out) return QW_ERR_INVALID_ARGUMENT;
+    out[0] = ctx->topk_pruned;
+    out[1] = ctx->topk_unpruned;
+    out[2] = ctx->topk_last_emitted;
+    out[3] = ctx->topk_last_matched;
     return QW_OK;
 }
 
