@@ -90,6 +90,10 @@ enum AggKindDev : uint32_t {
     AGGD_PERC = 6
 };
 constexpr uint32_t AGG_MAX_RANGES = 16;
+// bytes of one stats slot {u64 cnt, f64 sum, u64 min_s, u64 max_s, f64 sum_sq}
+// (AggDev::n_sub below). Plain int: it stands where the literal stood, so
+// the index arithmetic around it keeps its types.
+constexpr int STATS_SLOT_BYTES = 40;
 
 struct AggDev {
     uint32_t kind;
@@ -212,10 +216,13 @@ struct QueryDev {
     uint32_t _pad_prune;
 };
 
-// byte offset of the pruning bound inside the 64-byte cand_count header
-// (u32 words 0..2 are cand_count, the survivors count and the search_after
-// band count)
+// the 64-byte cand_count header at results + cand_count_off: three u32
+// counters, then the pruning bound (u64) at byte TOPK_BOUND_OFF
 constexpr uint32_t TOPK_BOUND_OFF = 16;
 constexpr uint32_t TOPK_PRUNE_MAX_K = 64;
+inline uint32_t* cand_hdr_candidates(uint8_t* hdr) { return (uint32_t*)hdr; }
+inline uint32_t* cand_hdr_survivors(uint8_t* hdr) { return (uint32_t*)hdr + 1; }
+// candidates left inside the search_after cursor band
+inline uint32_t* cand_hdr_cursor_band(uint8_t* hdr) { return (uint32_t*)hdr + 2; }
 
 }  // namespace qw

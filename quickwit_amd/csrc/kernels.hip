@@ -437,7 +437,8 @@ __device__ __forceinline__ void terms_subs_add(const QueryDev& q, const AggDev& 
         }
         double sv = agg_value(q, a.sub_values_off[si], a.sub_width[si],
                               a.sub_is_i64[si], d);
-        stats_slot_add(q.results + a.sub_out + (ord * a.n_sub + si) * 40, sv);
+        stats_slot_add(
+            q.results + a.sub_out + (ord * a.n_sub + si) * STATS_SLOT_BYTES, sv);
     }
 }
 
@@ -1004,7 +1005,7 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
                                     continue;
                                 }
                                 uint8_t* slot = q.results + a.sub_out +
-                                                (uint64_t(idx) * a.n_sub + si) * 40;
+                                                (uint64_t(idx) * a.n_sub + si) * STATS_SLOT_BYTES;
                                 atomicAdd((unsigned long long*)slot, 1ull);
                                 atomicAdd((double*)(slot + 8), sv);
                                 atomicMin((unsigned long long*)(slot + 16),
@@ -1310,13 +1311,22 @@ extern "C" __global__ void k_bitmap_combine(uint32_t* dst, const uint32_t* src,
 }
 
 // ----------------------------------------------------- top-K selection passes
+// One body per pass, templated on RW = u64 words per candidate record:
+// 1 = narrow (8B key|doc), 2 = wide (16B {u64 key, u64 aux}). The selection
+// key is always word 0 of the record. The kernels read blockDim.x themselves
+// and hand it down as `bdim`: the compiler folds it to the plain dispatch
+// field only where it is read inside a __global__ function.
+
 // histogram of the top 12 bits (after `shift`) of candidates matching
 // (key >> prefix_shift) == prefix
-extern "C" __global__ void k_cand_hist(const uint64_t* cand, const uint32_t* n_ptr,
-                                       uint64_t prefix, uint32_t prefix_bits,
-                                       uint32_t* hist) {
+template <uint32_t RW>
+__device__ __forceinline__ void cand_hist_body(uint32_t bdim, const uint64_t* cand,
+                                               const uint32_t* n_ptr,
+                                               uint64_t prefix,
+                                               uint32_t prefix_bits,
+                                               uint32_t* hist) {
     __shared__ uint32_t lh[TOPK_BINS];
-    for (uint32_t i = threadIdx.x; i < TOPK_BINS; i += blockDim.x) lh[i] = 0;
+    for (uint32_t i = threadIdx.x; i < TOPK_BINS; i += bdim) lh[i] = 0;
     __syncthreads();
     uint32_t n = *n_ptr;  // device-side count: pass 0 is enqueued without a
                           // host round trip for the candidate count
@@ -1324,9 +1334,9 @@ extern "C" __global__ void k_cand_hist(const uint64_t* cand, const uint32_t* n_p
     // per-thread run cache: score keys concentrate into few bins, so
     // consecutive samples often repeat a bin — batch the LDS atomics
     uint32_t last_bin = 0xFFFFFFFFu, acc = 0;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += gridDim.x * blockDim.x) {
-        uint64_t k = cand[i];
+    for (uint32_t i = blockIdx.x * bdim + threadIdx.x; i < n;
+         i += gridDim.x * bdim) {
+        uint64_t k = cand[RW * i];
         if (prefix_bits && (k >> (64 - prefix_bits)) != prefix) continue;
         uint32_t b = uint32_t(k >> shift) & (TOPK_BINS - 1);
         if (b == last_bin) ++acc;
@@ -1338,45 +1348,22 @@ extern "C" __global__ void k_cand_hist(const uint64_t* cand, const uint32_t* n_p
     }
     if (acc) atomicAdd(&lh[last_bin], acc);
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < TOPK_BINS; i += blockDim.x)
+    for (uint32_t i = threadIdx.x; i < TOPK_BINS; i += bdim)
         if (lh[i]) atomicAdd(&hist[i], lh[i]);
 }
 
-// wide-record (16B {u64 key, u64 aux}) variants of the selection passes
-extern "C" __global__ void k_cand_hist_w(const uint64_t* cand, const uint32_t* n_ptr,
-                                         uint64_t prefix, uint32_t prefix_bits,
-                                         uint32_t* hist) {
-    __shared__ uint32_t lh[TOPK_BINS];
-    for (uint32_t i = threadIdx.x; i < TOPK_BINS; i += blockDim.x) lh[i] = 0;
-    __syncthreads();
-    uint32_t n = *n_ptr;
-    uint32_t shift = 64 - prefix_bits - 12;
-    uint32_t last_bin = 0xFFFFFFFFu, acc = 0;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += gridDim.x * blockDim.x) {
-        uint64_t k = cand[2 * i];
-        if (prefix_bits && (k >> (64 - prefix_bits)) != prefix) continue;
-        uint32_t b = uint32_t(k >> shift) & (TOPK_BINS - 1);
-        if (b == last_bin) ++acc;
-        else {
-            if (acc) atomicAdd(&lh[last_bin], acc);
-            last_bin = b;
-            acc = 1;
-        }
-    }
-    if (acc) atomicAdd(&lh[last_bin], acc);
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < TOPK_BINS; i += blockDim.x)
-        if (lh[i]) atomicAdd(&hist[i], lh[i]);
-}
-
-extern "C" __global__ void k_cand_compact_w(const uint64_t* cand, uint32_t n,
-                                            uint64_t floor_key, uint64_t ceil_key,
-                                            uint64_t* out, uint32_t* out_count,
-                                            uint32_t cap) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += gridDim.x * blockDim.x) {
-        uint64_t k = cand[2 * i];
+// compact candidates with floor_key <= key <= ceil_key into out (bounded by
+// cap); wide records carry their aux word along
+template <uint32_t RW>
+__device__ __forceinline__ void cand_compact_body(uint32_t bdim,
+                                                  const uint64_t* cand, uint32_t n,
+                                                  uint64_t floor_key,
+                                                  uint64_t ceil_key, uint64_t* out,
+                                                  uint32_t* out_count,
+                                                  uint32_t cap) {
+    for (uint32_t i = blockIdx.x * bdim + threadIdx.x; i < n;
+         i += gridDim.x * bdim) {
+        uint64_t k = cand[RW * i];
         bool take = k >= floor_key && k <= ceil_key;
         uint64_t mask = __ballot(take);
         uint32_t nw = __popcll(mask);
@@ -1388,34 +1375,34 @@ extern "C" __global__ void k_cand_compact_w(const uint64_t* cand, uint32_t n,
         if (take) {
             uint32_t off = base + __popcll(mask & ((1ull << lane_id()) - 1ull));
             if (off < cap) {
-                out[2 * off] = k;
-                out[2 * off + 1] = cand[2 * i + 1];
+                out[RW * off] = k;
+                if (RW == 2) out[2 * off + 1] = cand[2 * i + 1];
             }
         }
     }
 }
 
-// compact candidates with key >= floor_key into out (bounded by cap)
+extern "C" __global__ void k_cand_hist(const uint64_t* cand, const uint32_t* n_ptr,
+                                       uint64_t prefix, uint32_t prefix_bits,
+                                       uint32_t* hist) {
+    cand_hist_body<1>(blockDim.x, cand, n_ptr, prefix, prefix_bits, hist);
+}
+extern "C" __global__ void k_cand_hist_w(const uint64_t* cand, const uint32_t* n_ptr,
+                                         uint64_t prefix, uint32_t prefix_bits,
+                                         uint32_t* hist) {
+    cand_hist_body<2>(blockDim.x, cand, n_ptr, prefix, prefix_bits, hist);
+}
 extern "C" __global__ void k_cand_compact(const uint64_t* cand, uint32_t n,
                                           uint64_t floor_key, uint64_t ceil_key,
                                           uint64_t* out, uint32_t* out_count,
                                           uint32_t cap) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += gridDim.x * blockDim.x) {
-        uint64_t k = cand[i];
-        bool take = k >= floor_key && k <= ceil_key;
-        uint64_t mask = __ballot(take);
-        uint32_t nw = __popcll(mask);
-        if (!nw) continue;
-        uint32_t leader = __ffsll((unsigned long long)mask) - 1;
-        uint32_t base;
-        if (lane_id() == leader) base = atomicAdd(out_count, nw);
-        base = __shfl(base, leader, 64);
-        if (take) {
-            uint32_t off = __popcll(mask & ((1ull << lane_id()) - 1ull));
-            if (base + off < cap) out[base + off] = k;
-        }
-    }
+    cand_compact_body<1>(blockDim.x, cand, n, floor_key, ceil_key, out, out_count, cap);
+}
+extern "C" __global__ void k_cand_compact_w(const uint64_t* cand, uint32_t n,
+                                            uint64_t floor_key, uint64_t ceil_key,
+                                            uint64_t* out, uint32_t* out_count,
+                                            uint32_t cap) {
+    cand_compact_body<2>(blockDim.x, cand, n, floor_key, ceil_key, out, out_count, cap);
 }
 
 }  // namespace qw

@@ -25,7 +25,6 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <list>
 #include <map>
 #include <memory>
@@ -852,6 +851,9 @@ struct AggPlan {
     std::vector<const FastFieldView*> fields;
     // composite aggs: per-source column views (null for other kinds)
     std::vector<std::array<const FastFieldView*, 4>> comp_fields;
+    // composite aggs: per-source bit widths of the packed key (decode reads
+    // these back instead of re-deriving them)
+    std::vector<std::array<uint32_t, 4>> comp_width;
     // percentiles: per-agg gamma^k boundary doubles (appended to scratch;
     // empty for aggs without a sketch)
     std::vector<std::vector<double>> pbounds;
@@ -888,6 +890,7 @@ static AggPlan plan_aggs(const SplitView& sv, const std::string& agg_json,
         const FastFieldView* f = sv.fast_field(d.field);
         ap.fields.push_back(f);
         ap.comp_fields.push_back({nullptr, nullptr, nullptr, nullptr});
+        ap.comp_width.push_back({0, 0, 0, 0});
         ap.pbounds.emplace_back();
         AggDev a{};
         a.lds_slot = 0xFF;
@@ -948,7 +951,8 @@ static AggPlan plan_aggs(const SplitView& sv, const std::string& agg_json,
                         : sf->type == FastFieldView::F64 ? 2
                                                          : 1;
                     a.c_shift[si] = acc;
-                    acc += comp_key_bits(n_values);
+                    ap.comp_width.back()[si] = comp_key_bits(n_values);
+                    acc += ap.comp_width.back()[si];
                 }
                 if (acc > 63)
                     throw std::runtime_error(
@@ -1176,16 +1180,18 @@ static AggPlan plan_aggs(const SplitView& sv, const std::string& agg_json,
                 a.n_buckets = 0;
             }
         }
-        // layout: counts u64[n_buckets] (METRIC: one 40 B stats slot) |
-        // matched u64 | subs n_buckets*n_sub*40
+        // layout: counts u64[n_buckets] (METRIC: one stats slot) |
+        // matched u64 | subs n_buckets*n_sub*STATS_SLOT_BYTES
         a.counts_out = off;
-        off += a.kind == AGGD_METRIC ? 40 : uint64_t(a.n_buckets) * 8;
+        off += a.kind == AGGD_METRIC ? STATS_SLOT_BYTES
+                                     : uint64_t(a.n_buckets) * 8;
         a.matched_out = off;
         off += 8;
         a.sub_out = off;
         // AGGD_COMP uses n_sub for its sources and n_buckets for the hash
         // table words — no per-bucket stats region
-        if (a.kind != AGGD_COMP) off += uint64_t(a.n_buckets) * a.n_sub * 40;
+        if (a.kind != AGGD_COMP)
+            off += uint64_t(a.n_buckets) * a.n_sub * STATS_SLOT_BYTES;
         if (a.p_si != 0xFF) {
             a.p_out = off;
             off += uint64_t(a.n_buckets) * (a.p_n_keys + 1) * 8;
@@ -1233,7 +1239,8 @@ static AggPlan plan_aggs(const SplitView& sv, const std::string& agg_json,
         for (uint64_t b = 0; b < a.n_buckets; ++b)
             for (uint32_t s = 0; s < a.n_sub; ++s) {
                 if (s == a.p_si) continue;  // percentiles slot: stays zero
-                uint64_t slot = a.sub_out - out_base + (b * a.n_sub + s) * 40;
+                uint64_t slot = a.sub_out - out_base +
+                                (b * a.n_sub + s) * STATS_SLOT_BYTES;
                 memcpy(&ap.init[slot + 16], &ones, 8);  // min slot: max sortable
                 // max slot stays 0 (= most negative sortable)
             }
@@ -1616,24 +1623,36 @@ static void collect_required_terms(
     }
 }
 
-static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
-                                    const pb::SearchRequest& req, const Schema& schema) {
-    SplitResult out;
-    auto t0 = std::chrono::steady_clock::now();
-    static const bool timing = getenv("QW_TIMING") != nullptr;
-    auto tprev = t0;
-    auto mark = [&](const char* what) {
+// ------------------------------------------------------------ leaf stages
+// search_split_gpu (end of this section) is a short driver over the stages
+// below. Each stage names its inputs and outputs; none keeps a reference
+// into another stage's locals.
+
+// QW_TIMING=1 stage log; logs are compared by label (profiles/README.md)
+struct StageTimer {
+    using Clock = std::chrono::steady_clock;
+    Clock::time_point t0 = Clock::now(), tprev = t0;
+    void mark(const char* what) {
+        static const bool timing = getenv("QW_TIMING") != nullptr;
         if (!timing) return;
-        auto now = std::chrono::steady_clock::now();
+        auto now = Clock::now();
         fprintf(stderr, "[qw_timing] %-18s %8.1f us\n", what,
                 std::chrono::duration_cast<std::chrono::nanoseconds>(now - tprev)
                         .count() /
                     1e3);
         tprev = now;
-    };
-    const SplitView& sv = ds.view;
-    ctx->hitsets.begin_query();  // unpin previous query's bitmap entries
+    }
+    uint64_t micros() const {
+        return uint64_t(std::chrono::duration_cast<std::chrono::microseconds>(
+                            Clock::now() - t0)
+                            .count());
+    }
+};
 
+// request -> PlanNode: the query AST, the request's timestamp bounds as a
+// RANGE filter, and the absence-cache short circuit
+static PlanNode leaf_plan(qw_ctx* ctx, const SplitView& sv,
+                          const pb::SearchRequest& req, const Schema& schema) {
     PlanNode plan = parse_query_ast(req.query_ast, schema);
     if ((req.start_timestamp || req.end_timestamp) && !schema.timestamp_field.empty()) {
         // leaf.rs:977 rewrite_request: [start,end) seconds over the ts column
@@ -1659,27 +1678,72 @@ static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
     // term proven absent by an earlier search short-circuits this split —
     // replace the plan with MATCH_NONE so the standard empty-response path
     // (shaped agg blob, stats) runs with no kernel and no dict lookups
-    {
-        std::vector<std::pair<std::string, std::string>> reqs;
-        collect_required_terms(plan, reqs);
-        bool hit = false;
-        for (auto& ft : reqs)
-            if (ctx->absence.keys.count(
-                    AbsenceCache::key(sv.split_id, ft.first, ft.second))) {
-                hit = true;
-                break;
-            }
-        if (!reqs.empty()) (hit ? ctx->absence.hits : ctx->absence.misses)++;
-        if (hit) {
-            PlanNode none;
-            none.kind = PlanNode::MATCH_NONE;
-            plan = std::move(none);
+    std::vector<std::pair<std::string, std::string>> reqs;
+    collect_required_terms(plan, reqs);
+    bool hit = false;
+    for (auto& ft : reqs)
+        if (ctx->absence.keys.count(
+                AbsenceCache::key(sv.split_id, ft.first, ft.second))) {
+            hit = true;
+            break;
+        }
+    if (!reqs.empty()) (hit ? ctx->absence.hits : ctx->absence.misses)++;
+    if (hit) {
+        PlanNode none;
+        none.kind = PlanNode::MATCH_NONE;
+        plan = std::move(none);
+    }
+    return plan;
+}
+
+// sort orders of a request (0 asc, 1 desc); doc-id order defaults to desc
+static void request_sort_orders(const pb::SearchRequest& req, int* order1,
+                                int* order2) {
+    *order1 = req.sort_fields.empty() ? 1 : req.sort_fields[0].sort_order;
+    *order2 = req.sort_fields.size() > 1 ? req.sort_fields[1].sort_order : 1;
+}
+
+// how the request sorts, and its search_after cursor in the sort fields'
+// u64 domains
+struct SortPlan {
+    std::vector<SortSpec> specs;
+    int order1 = 1, order2 = 1;
+    bool scoring = false;  // some sort field is _score
+    // narrow (8B) candidate records embed the f32 _score key + doc tiebreak:
+    // exact device-side selection. fast-field or two-field sorts use wide
+    // (16B) records selected by primary key only; exact order over the
+    // survivors is re-established on host (kernels.hip wide_sort_key).
+    bool wide = false;
+    // effective cursor: null when the request has none, or when it sorts
+    // before every value (CursorKey::disabled)
+    const pb::PartialHit* after = nullptr;
+    CursorKey ck1, ck2;
+
+    static SortFieldKind kind_of(const SortSpec& s) {
+        if (s.comp == SortSpec::SCORE) return SortFieldKind::SCORE;
+        if (s.comp != SortSpec::FAST_FIELD || !s.ff) return SortFieldKind::NONE;
+        switch (s.ff->type) {
+            case FastFieldView::U64: return SortFieldKind::U64;
+            case FastFieldView::I64: return SortFieldKind::I64;
+            case FastFieldView::DATETIME: return SortFieldKind::DATETIME;
+            case FastFieldView::F64: return SortFieldKind::F64;
+            case FastFieldView::MIXED: return SortFieldKind::MIXED;
+            default: return SortFieldKind::STR;
         }
     }
+    bool mixed(size_t i) const {
+        return specs.size() > i && kind_of(specs[i]) == SortFieldKind::MIXED;
+    }
+    // ascending primary sort: candidate keys are flipped on the device.
+    // make_sort_plan only ever sets comp to SCORE or FAST_FIELD, so a
+    // `comp != DOC_ID` term would be implied by !specs.empty().
+    bool sort_asc() const { return !specs.empty() && order1 == 0; }
+};
 
+static SortPlan make_sort_plan(const SplitView& sv, const pb::SearchRequest& req) {
     if (req.sort_fields.size() > 2)
         throw std::runtime_error("more than two sort fields (search.proto:269)");
-    std::vector<SortSpec> specs;
+    SortPlan sp;
     for (auto& sf : req.sort_fields) {
         SortSpec s;
         s.order = sf.sort_order;
@@ -1688,22 +1752,34 @@ static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
             s.comp = SortSpec::FAST_FIELD;
             s.ff = sv.fast_field(sf.field_name);
         }
-        specs.push_back(s);
+        sp.scoring |= s.comp == SortSpec::SCORE;
+        sp.specs.push_back(s);
     }
-    bool scoring = false;
-    for (auto& s : specs) scoring |= s.comp == SortSpec::SCORE;
-    int order1 = specs.empty() ? 1 : specs[0].order;
-    int order2 = specs.size() > 1 ? specs[1].order : 1;
-    // narrow (8B) candidate records embed the f32 _score key + doc tiebreak:
-    // exact device-side selection. fast-field or two-field sorts use wide
-    // (16B) records selected by primary key only; exact order over the
-    // survivors is re-established on host (kernels.hip wide_sort_key).
-    bool wide = (!specs.empty() && specs[0].comp == SortSpec::FAST_FIELD) ||
-                specs.size() > 1;
+    request_sort_orders(req, &sp.order1, &sp.order2);
+    sp.wide = (!sp.specs.empty() && sp.specs[0].comp == SortSpec::FAST_FIELD) ||
+              sp.specs.size() > 1;
+    // typed cursor conversion into the sort fields' u64 domains
+    // (convert_to_u64_ff_val, collector.rs:214-340)
+    if (req.search_after) {
+        sp.after = &*req.search_after;
+        if (!sp.specs.empty())
+            sp.ck1 = convert_cursor_key(sp.after->sort_value,
+                                        SortPlan::kind_of(sp.specs[0]), sp.order1);
+        if (sp.specs.size() > 1)
+            sp.ck2 = convert_cursor_key(sp.after->sort_value2,
+                                        SortPlan::kind_of(sp.specs[1]), sp.order2);
+        if (sp.ck1.disabled) sp.after = nullptr;  // cursor before all values
+    }
+    return sp;
+}
 
+// plan -> FlatQuery, with every bitmap-backed predicate resolved
+static FlatQuery flatten_or_bitmap(qw_ctx* ctx, const DeviceSplit& ds,
+                                   const PlanNode& plan, const Schema& schema,
+                                   bool scoring) {
     FlatQuery fq;
     try {
-        fq = flatten(sv, plan, scoring);
+        fq = flatten(ds.view, plan, scoring);
     } catch (const std::exception& e) {
         std::string msg = e.what();
         if (scoring || msg.find("flatten") == std::string::npos) throw;
@@ -1719,103 +1795,63 @@ static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
         p.abs_bitmap = (uint64_t)bmp;
         fq.preds.push_back(p);
     }
-    // report required terms flattening proved absent; the caller inserts
-    // into the absence cache (for multi-segment splits only terms absent
-    // from EVERY segment qualify)
-    out.absent_required = fq.absent_required;
     // CACHE nodes in filter position -> device HitSet bitmaps (PRED_BITSET)
     for (const PlanNode* cn : fq.cache_nodes) {
         PredDev p{};
         p.type = PRED_BITSET;
-        p.abs_bitmap = (uint64_t)bitmap_eval(ctx, const_cast<DeviceSplit&>(ds),
-                                             cn->cache_inner.front(), schema);
+        p.abs_bitmap =
+            (uint64_t)bitmap_eval(ctx, ds, cn->cache_inner.front(), schema);
         fq.preds.push_back(p);
     }
-    uint64_t leaf_max_hits = req.max_hits + req.start_offset;
+    return fq;
+}
 
-    if (fq.match_none || sv.num_docs == 0) {
-        if (req.aggregation_request) {
-            // empty-but-shaped blob, like the oracle over an empty match set
-            for (const AggDef& d : parse_agg_request(*req.aggregation_request)) {
-                AggResult r;
-                r.name = d.name;
-                r.kind = d.kind == AggDef::TERMS         ? 3
-                         : d.kind == AggDef::CARDINALITY ? 3
-                         : d.kind == AggDef::COMPOSITE   ? 3
-                         : d.kind == AggDef::RANGE       ? 4
-                         : d.kind == AggDef::METRIC
-                             ? (d.metric.kind == MetricAgg::PERCENTILES ? 6 : 5)
-                         : d.kind == AggDef::HISTOGRAM ? 2
-                                                       : 1;
-                if (d.kind == AggDef::COMPOSITE) r.key_kind = 9;
-                for (auto& s : d.sub) {
-                    r.sub_names.push_back(s.name);
-                    r.sub_kinds.push_back(
-                        s.kind == MetricAgg::PERCENTILES ? 1 : 0);
-                }
-                out.aggs.aggs.push_back(std::move(r));
-            }
-            out.has_aggs = true;
-        }
-        out.micros = uint64_t(std::chrono::duration_cast<std::chrono::microseconds>(
-                                  std::chrono::steady_clock::now() - t0)
-                                  .count());
-        return out;
+// AggResult::kind of an aggregation (qagg_format.h)
+static uint8_t agg_result_kind(const AggDef& d) {
+    switch (d.kind) {
+        case AggDef::TERMS:
+        case AggDef::CARDINALITY:
+        case AggDef::COMPOSITE: return 3;
+        case AggDef::RANGE: return 4;
+        case AggDef::METRIC:
+            return d.metric.kind == MetricAgg::PERCENTILES ? 6 : 5;
+        case AggDef::HISTOGRAM: return 2;
+        case AggDef::DATE_HISTOGRAM: return 1;
     }
+    return 1;
+}
 
-    AggPlan ap;
-    bool do_aggs = req.aggregation_request.has_value();
-
-    uint32_t n_tiles = (sv.num_docs + TILE_DOCS - 1) / TILE_DOCS;
-    bool pure_match_all = fq.match_all && fq.preds.empty() && fq.terms.empty();
-    // hits trivially enumerable only under doc-id order (leaf.rs default)
-    const pb::PartialHit* after =
-        req.search_after ? &*req.search_after : nullptr;
-    // typed cursor conversion into the sort fields' u64 domains
-    // (convert_to_u64_ff_val, collector.rs:214-340)
-    auto kind_of = [&](const SortSpec& s) {
-        if (s.comp == SortSpec::SCORE) return SortFieldKind::SCORE;
-        if (s.comp != SortSpec::FAST_FIELD || !s.ff) return SortFieldKind::NONE;
-        switch (s.ff->type) {
-            case FastFieldView::U64: return SortFieldKind::U64;
-            case FastFieldView::I64: return SortFieldKind::I64;
-            case FastFieldView::DATETIME: return SortFieldKind::DATETIME;
-            case FastFieldView::F64: return SortFieldKind::F64;
-            case FastFieldView::MIXED: return SortFieldKind::MIXED;
-            default: return SortFieldKind::STR;
+// empty-but-shaped blob, like the oracle over an empty match set. Unlike
+// decode_aggs it tags sub_kinds for every aggregation kind: plan_aggs never
+// ran here, so the combinations it rejects are still encoded as requested.
+static void empty_agg_shapes(const std::string& agg_json,
+                             IntermediateAggResults& out) {
+    for (const AggDef& d : parse_agg_request(agg_json)) {
+        AggResult r;
+        r.name = d.name;
+        r.kind = agg_result_kind(d);
+        if (d.kind == AggDef::COMPOSITE) r.key_kind = 9;
+        for (auto& s : d.sub) {
+            r.sub_names.push_back(s.name);
+            r.sub_kinds.push_back(s.kind == MetricAgg::PERCENTILES ? 1 : 0);
         }
-    };
-    CursorKey ck1, ck2;
-    if (after) {
-        ck1 = specs.empty() ? CursorKey{}
-                            : convert_cursor_key(after->sort_value,
-                                                 kind_of(specs[0]), order1);
-        ck2 = specs.size() < 2 ? CursorKey{}
-                               : convert_cursor_key(after->sort_value2,
-                                                    kind_of(specs[1]), order2);
-        if (ck1.disabled) after = nullptr;  // cursor before all values
+        out.aggs.push_back(std::move(r));
     }
-    bool trivial_hits = pure_match_all && specs.empty() && !after;
-    // candidate collection: needed unless hits are trivially enumerable
-    bool collect = leaf_max_hits > 0 && !trivial_hits && !fq.match_none;
-    bool need_kernel = !pure_match_all || do_aggs || collect;
+}
 
-    // ---- scratch assembly (descriptors + ktabs + block ranges), one H2D
-    std::vector<TermDev> terms(fq.terms.size());
+// device term descriptors + the BM25 K tables they index
+struct TermTables {
+    std::vector<TermDev> terms;
+    std::vector<float> ktabs;  // 256 f32 per fq.ktab_fields entry, >= 1 table
     uint32_t n_must = 0, n_must_not = 0;
-    std::vector<float> ktabs(fq.ktab_fields.size() * 0);  // filled below
+};
 
-    // K tables per field actually referenced by scored terms
-    std::vector<const TextFieldView*> ktab_fields;
-    auto ktab_idx_of = [&](const TextFieldView* f) {
-        for (size_t i = 0; i < ktab_fields.size(); ++i)
-            if (ktab_fields[i] == f) return uint32_t(i);
-        ktab_fields.push_back(f);
-        return uint32_t(ktab_fields.size() - 1);
-    };
+static TermTables build_term_tables(const SplitView& sv, FlatQuery& fq) {
+    TermTables tt;
+    tt.terms.resize(fq.terms.size());
     for (size_t i = 0; i < fq.terms.size(); ++i) {
         const FlatQuery::FTerm& t = fq.terms[i];
-        TermDev& d = terms[i];
+        TermDev& d = tt.terms[i];
         d.role = t.role;
         d.n_blocks = t.f->h_n_blocks[t.tid];
         d.skip_off = t.f->skip.off + t.f->h_skip_off[t.tid];
@@ -1823,813 +1859,913 @@ static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
         d.norms_off = t.f->has_norms ? t.f->fieldnorms.off : 0;
         d.weight = t.weight;
         d.grp = t.grp;
-        d.ktab_idx = fq.scoring ? ktab_idx_of(t.f) : 0;
-        n_must += t.role == ROLE_MUST;
-        n_must_not += t.role == ROLE_MUST_NOT;
+        // K tables per field actually referenced by scored terms
+        d.ktab_idx = fq.scoring ? fq.ktab_for(t.f) : 0;
+        tt.n_must += t.role == ROLE_MUST;
+        tt.n_must_not += t.role == ROLE_MUST_NOT;
     }
-    ktabs.resize(std::max<size_t>(1, ktab_fields.size()) * 256, 0.f);
-    for (size_t k = 0; k < ktab_fields.size(); ++k) {
-        const TextFieldView* f = ktab_fields[k];
+    tt.ktabs.resize(std::max<size_t>(1, fq.ktab_fields.size()) * 256, 0.f);
+    for (size_t k = 0; k < fq.ktab_fields.size(); ++k) {
+        const TextFieldView* f = fq.ktab_fields[k];
         double avgdl = f->total_tokens > 0 && sv.num_docs > 0
                            ? double(f->total_tokens) / double(sv.num_docs)
                            : 0.0;
         const double K1 = 1.2, B = 0.75;
         for (int i = 0; i < 256; ++i) {
             double fn = double(FIELDNORM_TABLE.v[i]);
-            ktabs[k * 256 + i] =
+            tt.ktabs[k * 256 + i] =
                 float(K1 * (1.0 - B + B * fn / (avgdl > 0 ? avgdl : 1.0)));
         }
     }
+    return tt;
+}
 
-    // scratch layout
-    size_t off_terms = 0;
-    size_t off_preds = off_terms + terms.size() * sizeof(TermDev);
-    size_t off_aggs = off_preds + fq.preds.size() * sizeof(PredDev);
-    // aggs descriptors appended after planning (below)
-    // results layout
-    size_t r_tile_counts = 0;
-    size_t r_cand_count = r_tile_counts + size_t(n_tiles) * 4;
-    r_cand_count = (r_cand_count + 63) & ~size_t(63);
-    size_t r_hist = r_cand_count + 64;  // cand_count u32 + survivors count u32
-    size_t r_agg = r_hist + TOPK_BINS * 4;
-    r_agg = (r_agg + 63) & ~size_t(63);
+// byte offsets of one query's two device regions
+struct ScratchLayout {
+    // query scratch (one H2D): TermDev[] | PredDev[] | AggDev[] | K tables |
+    // percentiles boundary tables
+    size_t off_terms = 0, off_preds = 0, off_aggs = 0, off_ktabs = 0;
+    size_t scratch_bytes = 0;
+    // results: tile counts | 64 B cand_count header (gpu_types.h) | selection
+    // histogram | aggregation output | candidate records
+    size_t r_tile_counts = 0, r_cand_count = 0, r_hist = 0, r_agg = 0, r_cand = 0;
+    size_t results_bytes = 0;
+    size_t cand_cap = 0;  // candidate records (0 = no collection)
+    size_t cand_rec = 8;  // bytes per record
+};
 
-    if (do_aggs)
-        ap = plan_aggs(sv, *req.aggregation_request, ctx->agg_bucket_limit, r_agg);
-    size_t r_cand = r_agg + ((ap.out_bytes + 63) & ~size_t(63));
-    size_t cand_cap = collect ? sv.num_docs : 0;
-    size_t cand_rec = wide ? 16 : 8;
-    size_t results_bytes = r_cand + cand_cap * cand_rec;
+// the results offsets up to r_agg depend on the tile count alone; plan_aggs
+// needs r_agg as its output base before the rest can be laid out
+static ScratchLayout layout_results_head(uint32_t n_tiles) {
+    ScratchLayout L;
+    L.r_tile_counts = 0;
+    L.r_cand_count = L.r_tile_counts + size_t(n_tiles) * 4;
+    L.r_cand_count = (L.r_cand_count + 63) & ~size_t(63);
+    L.r_hist = L.r_cand_count + 64;
+    L.r_agg = L.r_hist + TOPK_BINS * 4;
+    L.r_agg = (L.r_agg + 63) & ~size_t(63);
+    return L;
+}
 
-    size_t off_ktabs = off_aggs + ap.devs.size() * sizeof(AggDev);
-    size_t scratch_bytes = off_ktabs + ktabs.size() * 4;
-    // percentiles boundary tables (gamma^k doubles the kernel searches)
-    scratch_bytes = (scratch_bytes + 7) & ~size_t(7);
+// completes the layout; also places each percentiles boundary table
+// (gamma^k doubles the kernel searches) and records it in ap.devs
+static void layout_finish(ScratchLayout& L, const TermTables& tt,
+                          const FlatQuery& fq, AggPlan& ap, size_t cand_cap,
+                          bool wide) {
+    L.r_cand = L.r_agg + ((ap.out_bytes + 63) & ~size_t(63));
+    L.cand_cap = cand_cap;
+    L.cand_rec = wide ? 16 : 8;
+    L.results_bytes = L.r_cand + L.cand_cap * L.cand_rec;
+
+    L.off_terms = 0;
+    L.off_preds = L.off_terms + tt.terms.size() * sizeof(TermDev);
+    L.off_aggs = L.off_preds + fq.preds.size() * sizeof(PredDev);
+    L.off_ktabs = L.off_aggs + ap.devs.size() * sizeof(AggDev);
+    L.scratch_bytes = L.off_ktabs + tt.ktabs.size() * 4;
+    L.scratch_bytes = (L.scratch_bytes + 7) & ~size_t(7);
     for (size_t i = 0; i < ap.devs.size(); ++i)
         if (!ap.pbounds[i].empty()) {
-            ap.devs[i].p_bound_off = scratch_bytes;
-            scratch_bytes += ap.pbounds[i].size() * 8;
+            ap.devs[i].p_bound_off = L.scratch_bytes;
+            L.scratch_bytes += ap.pbounds[i].size() * 8;
         }
+}
 
-    // dense positive base => eager predicate evaluation (kernels.hip):
-    // estimate the pre-predicate match density from the term dfs
-    {
-        double density = 1.0;
-        if (!fq.match_all && !fq.terms.empty()) {
-            double n = double(std::max<uint32_t>(sv.num_docs, 1));
-            double mind = 1.0, sum = 0.0;
-            bool has_must = false;
-            for (const FlatQuery::FTerm& t : fq.terms) {
-                double dfr = double(t.f->h_doc_freq[t.tid]) / n;
-                if (t.role == ROLE_MUST) {
-                    mind = std::min(mind, dfr);
-                    has_must = true;
-                } else if (t.role == ROLE_SHOULD) sum += dfr;
-            }
-            density = has_must ? mind
-                      : fq.msm > 0 ? std::min(1.0, sum)
-                                   : 1.0;
+// dense positive base => eager predicate evaluation (kernels.hip):
+// estimate the pre-predicate match density from the term dfs
+static void eager_pred_flags(const SplitView& sv, FlatQuery& fq) {
+    double density = 1.0;
+    if (!fq.match_all && !fq.terms.empty()) {
+        double n = double(std::max<uint32_t>(sv.num_docs, 1));
+        double mind = 1.0, sum = 0.0;
+        bool has_must = false;
+        for (const FlatQuery::FTerm& t : fq.terms) {
+            double dfr = double(t.f->h_doc_freq[t.tid]) / n;
+            if (t.role == ROLE_MUST) {
+                mind = std::min(mind, dfr);
+                has_must = true;
+            } else if (t.role == ROLE_SHOULD) sum += dfr;
         }
-        if (density >= 0.15)
-            for (PredDev& pr : fq.preds)
-                if (pr.type == PRED_RANGE_U64 || pr.type == PRED_RANGE_I64 ||
-                    pr.type == PRED_RANGE_F64)
-                    pr.flags |= PRED_EAGER;
+        density = has_must ? mind
+                  : fq.msm > 0 ? std::min(1.0, sum)
+                               : 1.0;
     }
+    if (density >= 0.15)
+        for (PredDev& pr : fq.preds)
+            if (pr.type == PRED_RANGE_U64 || pr.type == PRED_RANGE_I64 ||
+                pr.type == PRED_RANGE_F64)
+                pr.flags |= PRED_EAGER;
+}
 
-    mark("plan");
-    // per-term block ranges come from the split-level device cache
-    // (term_ranges_addr): first query pays the walk+upload, repeats don't
-    ctx->h_scratch.ensure(scratch_bytes);
-    uint8_t* scratch = ctx->h_scratch.p;
-    for (size_t i = 0; i < fq.terms.size(); ++i) {
-        const FlatQuery::FTerm& t = fq.terms[i];
-        terms[i].ranges_addr =
-            term_ranges_addr(ctx, ds, t.f, t.tid, n_tiles, sv.num_docs);
-    }
-    mark("ranges");
-
-    memcpy(scratch + off_terms, terms.data(), terms.size() * sizeof(TermDev));
-    memcpy(scratch + off_preds, fq.preds.data(),
+static void assemble_scratch(uint8_t* scratch, const ScratchLayout& L,
+                             const TermTables& tt, const FlatQuery& fq,
+                             const AggPlan& ap) {
+    memcpy(scratch + L.off_terms, tt.terms.data(),
+           tt.terms.size() * sizeof(TermDev));
+    memcpy(scratch + L.off_preds, fq.preds.data(),
            fq.preds.size() * sizeof(PredDev));
-    memcpy(scratch + off_aggs, ap.devs.data(), ap.devs.size() * sizeof(AggDev));
-    memcpy(scratch + off_ktabs, ktabs.data(), ktabs.size() * 4);
+    memcpy(scratch + L.off_aggs, ap.devs.data(), ap.devs.size() * sizeof(AggDev));
+    memcpy(scratch + L.off_ktabs, tt.ktabs.data(), tt.ktabs.size() * 4);
     for (size_t i = 0; i < ap.devs.size(); ++i)
         if (!ap.pbounds[i].empty())
-            memcpy(scratch + ap.devs[i].p_bound_off,
-                   ap.pbounds[i].data(), ap.pbounds[i].size() * 8);
+            memcpy(scratch + ap.devs[i].p_bound_off, ap.pbounds[i].data(),
+                   ap.pbounds[i].size() * 8);
+}
 
-    uint64_t matched = 0;
-    mark("assembly");
-    std::vector<uint64_t> top_keys;  // survivors, sorted best-first
-    std::function<void(uint64_t)> rerun_select;  // search_after retry hook
-    uint64_t sel_band_n = 0, sel_kwant = 0;
-    // prefetched selection pass-0 histogram, in pinned staging (async D2H
-    // to pageable memory degrades to a blocking staged copy)
-    ctx->h_surv.ensure(TOPK_BINS * 4);
-    uint32_t* hist0 = (uint32_t*)ctx->h_surv.p;
+// everything launch_leaf_tile needs for one query
+struct TileLaunch {
+    QueryDev q{};
+    // query-shape flags select the template instantiation whose dynamic
+    // LDS holds exactly the sections this shape touches (kernels.hip)
+    bool ns = false, nb = false, na = false;
+    uint32_t grid = 0;
+    const char* kname = "";  // kernel timer name
+};
 
-    if (need_kernel) {
-        qw_ensure_acct(ctx, ctx->d_scratch, scratch_bytes);
-        qw_ensure_acct(ctx, ctx->d_results, results_bytes);
-        HIP_CHECK(hipMemcpyAsync(ctx->d_scratch.p, scratch, scratch_bytes,
-                                 hipMemcpyHostToDevice, ctx->stream));
-        HIP_CHECK(hipMemsetAsync(ctx->d_results.p, 0, r_agg, ctx->stream));
-        if (do_aggs && ap.out_bytes)
-            HIP_CHECK(hipMemcpyAsync(ctx->d_results.p + r_agg, ap.init.data(),
-                                     ap.out_bytes, hipMemcpyHostToDevice, ctx->stream));
-
-        QueryDev q{};
-        q.split = ds.d_image;
-        q.scratch = ctx->d_scratch.p;
-        q.results = ctx->d_results.p;
-        q.num_docs = sv.num_docs;
-        q.n_tiles = n_tiles;
-        q.n_terms = uint32_t(terms.size());
-        q.n_must = fq.n_must_groups;  // group count (TermDev::grp)
-        q.n_must_not = n_must_not;
-        q.n_preds = uint32_t(fq.preds.size());
-        q.n_aggs = uint32_t(ap.devs.size());
-        q.msm = fq.msm;
-        q.scoring = fq.scoring ? 1 : 0;
-        q.match_all = fq.match_all ? 1 : 0;
-        q.collect_hits = collect ? 1 : 0;
-        q.sort_asc = (!specs.empty() && specs[0].comp != SortSpec::DOC_ID &&
-                      order1 == 0)
-                         ? 1
-                         : 0;
-        q.wide_cand = wide ? 1 : 0;
-        if (wide) {
-            const SortSpec& s0 = specs[0];
-            if (s0.comp == SortSpec::SCORE) {
-                q.sort_src = 1;
-            } else if (s0.ff) {
-                const FastFieldView* f = s0.ff;
-                if (f->multi)
-                    throw std::runtime_error(
-                        "sort by a multi-valued fast field not supported");
-                q.sort_values_off = f->values.off;
-                q.sort_nulls_off = f->nullable ? f->nulls.off : 0;
-                if (f->type == FastFieldView::STR) {
-                    q.sort_src = 2;
-                    q.sort_width = uint32_t(f->ord_width);
-                } else {
-                    // MIXED columns store f64-monotonic u64 keys: ascending
-                    // u64 order IS the numeric order -> device treats them
-                    // like a u64 column
-                    q.sort_src = f->type == FastFieldView::U64    ? 2
-                                 : f->type == FastFieldView::MIXED ? 2
-                                 : f->type == FastFieldView::F64  ? 4
-                                                                  : 3;
-                    q.sort_width = 8;
-                }
+// reads ctx->d_scratch / ctx->d_results: both must be sized already
+static TileLaunch fill_query_dev(qw_ctx* ctx, const DeviceSplit& ds,
+                                 const FlatQuery& fq, const SortPlan& sp,
+                                 const TermTables& tt, const AggPlan& ap,
+                                 const ScratchLayout& L, bool collect,
+                                 bool do_aggs, uint64_t leaf_max_hits,
+                                 uint32_t n_tiles) {
+    TileLaunch tl;
+    QueryDev& q = tl.q;
+    q.split = ds.d_image;
+    q.scratch = ctx->d_scratch.p;
+    q.results = ctx->d_results.p;
+    q.num_docs = ds.view.num_docs;
+    q.n_tiles = n_tiles;
+    q.n_terms = uint32_t(tt.terms.size());
+    q.n_must = fq.n_must_groups;  // group count (TermDev::grp)
+    q.n_must_not = tt.n_must_not;
+    q.n_preds = uint32_t(fq.preds.size());
+    q.n_aggs = uint32_t(ap.devs.size());
+    q.msm = fq.msm;
+    q.scoring = fq.scoring ? 1 : 0;
+    q.match_all = fq.match_all ? 1 : 0;
+    q.collect_hits = collect ? 1 : 0;
+    q.sort_asc = sp.sort_asc() ? 1 : 0;
+    q.wide_cand = sp.wide ? 1 : 0;
+    if (sp.wide) {
+        const SortSpec& s0 = sp.specs[0];
+        if (s0.comp == SortSpec::SCORE) {
+            q.sort_src = 1;
+        } else if (s0.ff) {
+            const FastFieldView* f = s0.ff;
+            if (f->multi)
+                throw std::runtime_error(
+                    "sort by a multi-valued fast field not supported");
+            q.sort_values_off = f->values.off;
+            q.sort_nulls_off = f->nullable ? f->nulls.off : 0;
+            if (f->type == FastFieldView::STR) {
+                q.sort_src = 2;
+                q.sort_width = uint32_t(f->ord_width);
             } else {
-                q.sort_src = 0;  // unknown field: every key is None
-            }
-        }
-        q.terms_off = off_terms;
-        q.preds_off = off_preds;
-        q.aggs_off = off_aggs;
-        q.ktabs_off = off_ktabs;
-        // LDS staging of fieldnorms + K tables for the scoring decode path
-        // (kernels.hip): enabled when every scored term's norms live in ONE
-        // section (single-field queries — the flagship shape) and the K
-        // tables fit the LDS budget. QW_NO_LDS_NORMS / QW_NO_LDS_KTAB are
-        // perf-experiment kill switches.
-        if (fq.scoring) {
-            // measured on MI355X at the 100M flagship: norms staging LOSES
-            // (the +8KB LDS drops occupancy 4->3 WGs/CU while the norm
-            // gathers already hit L2 — union covers ~25% of docs, ~16 hits
-            // per cacheline); ktab staging is noise. Both stay available as
-            // opt-in experiment switches (gpurun_out/r02_exp_variants.log).
-            static const bool want_norms = getenv("QW_LDS_NORMS") != nullptr;
-            static const bool want_ktab = getenv("QW_LDS_KTAB") != nullptr;
-            uint64_t common = 0;
-            bool uniform = true;
-            for (const TermDev& t : terms)
-                if (t.norms_off) {
-                    if (!common) common = t.norms_off;
-                    else if (common != t.norms_off) uniform = false;
-                }
-            q.norms_stage_off = (want_norms && uniform) ? common : 0;
-            q.n_ktabs = (want_ktab && ktab_fields.size() <= KTAB_LDS_MAX)
-                            ? uint32_t(ktab_fields.size())
-                            : 0;
-        }
-        q.tile_counts_off = r_tile_counts;
-        q.cand_count_off = r_cand_count;
-        q.cand_off = r_cand;
-        q.cand_cap = cand_cap;
-        q.hist_off = r_hist;
-        // prune candidates in the tile kernel: narrow records, small K, no
-        // cursor (the cursor band is cut out of ALL candidates afterwards),
-        // and a real candidate array
-        uint32_t prune_k = 0;
-        if (collect && !wide && !after && cand_cap > 0 && leaf_max_hits >= 1 &&
-            leaf_max_hits <= TOPK_PRUNE_MAX_K && ctx->topk_prune)
-            prune_k = uint32_t(leaf_max_hits);
-        q.prune_k = prune_k;
-
-        const char* kname = !fq.terms.empty() ? "union_bm25"
-                            : do_aggs         ? "column_agg"
-                                              : "range_filter";
-        // query-shape flags select the template instantiation whose dynamic
-        // LDS holds exactly the sections this shape touches (kernels.hip)
-        uint32_t n_should = uint32_t(terms.size()) - n_must - n_must_not;
-        bool ns = n_should > 0 || (fq.scoring && !terms.empty());
-        bool nb = n_must > 0 || n_must_not > 0;
-        bool na = do_aggs && !ap.devs.empty();
-        // agg workloads: capped grid so the once-per-workgroup LDS flush
-        // stays cheap (each WG owns several tiles). For PURE column scans
-        // (no posting decode) the grid also scales DOWN with the split
-        // size — the flush costs grid x buckets global atomics regardless
-        // of docs, which dominated small splits (256 WGs x 4 waves still
-        // fill the chip's 1024 resident-wave slots). Decode-carrying
-        // kernels keep the wide grid: fewer WGs serialize the per-tile
-        // decode loops and cost more than the flush saves (measured,
-        // config5 ablation).
-        uint32_t grid = n_tiles;
-        if (na)
-            grid = fq.terms.empty()
-                       ? std::min<uint32_t>(
-                             {n_tiles, 2048u,
-                              std::max<uint32_t>(256u, n_tiles / 8)})
-                       : std::min<uint32_t>(n_tiles, 2048u);
-        // straight-line agg path (kernels.hip): histo[0] int_fast LDS
-        // non-nullable no-subs (+ optional terms[1] LDS non-nullable)
-        if (na && !ap.devs.empty() && ap.devs[0].kind == AGGD_HISTO &&
-            ap.devs[0].lds_slot == 0 && ap.devs[0].int_fast &&
-            ap.devs[0].n_sub == 0 && ap.devs[0].nulls_off == 0 &&
-            ap.devs.size() <= 2 &&
-            (ap.devs.size() < 2 ||
-             (ap.devs[1].kind == AGGD_TERMS && ap.devs[1].lds_slot == 1 &&
-              ap.devs[1].nulls_off == 0 && ap.devs[1].offsets_off == 0 &&
-              ap.devs[1].n_buckets > 0)))
-            q.agg_fast = 1;
-        // terms-only straight-line path (config5's shape): one LDS terms
-        // agg, non-nullable single-valued ord column, no subs
-        if (na && ap.devs.size() == 1 && ap.devs[0].kind == AGGD_TERMS &&
-            ap.devs[0].lds_slot == 1 && ap.devs[0].n_sub == 0 &&
-            ap.devs[0].nulls_off == 0 && ap.devs[0].offsets_off == 0 &&
-            ap.devs[0].n_buckets > 0)
-            q.agg_fast = 1;
-        static const bool agg_nt = getenv("QW_AGG_NT") != nullptr;
-        q.agg_nt = agg_nt ? 1 : 0;
-        static const bool nt_decode = getenv("QW_NT_DECODE") != nullptr;
-        q.nt_decode = nt_decode ? 1 : 0;
-        HIP_CHECK(hipEventRecord(ctx->ev_start, ctx->stream));
-        launch_leaf_tile(ns, nb, na, collect, dim3(grid), ctx->stream, q, 0u,
-                         n_tiles, 1u);
-        HIP_CHECK(hipEventRecord(ctx->ev_stop, ctx->stream));
-        HIP_CHECK(hipGetLastError());
-
-        // enqueue top-K histogram pass 0 behind the main kernel (count read
-        // device-side) so its result arrives with the same synchronize
-        // (kept when pruning: the 100M flagship still emits ~130k records,
-        // above the 16384 no-refinement threshold, and a pass over that few
-        // costs far less than the extra round trip rerun_select would need)
-        bool hist0_valid = false;
-        if (collect && !after) {
-            uint64_t* d_cand0 = (uint64_t*)(ctx->d_results.p + r_cand);
-            uint32_t* d_hist0 = (uint32_t*)(ctx->d_results.p + r_hist);
-            uint32_t* d_n0 = (uint32_t*)(ctx->d_results.p + r_cand_count);
-            HIP_CHECK(hipMemsetAsync(d_hist0, 0, TOPK_BINS * 4, ctx->stream));
-            // candidate count is device-side only at this point: size the
-            // grid for the worst case (every doc a candidate)
-            uint32_t hgrid =
-                std::min<uint32_t>(512, (sv.num_docs + 4095) / 4096);
-            if (wide)
-                hipLaunchKernelGGL(k_cand_hist_w, dim3(hgrid), dim3(256), 0,
-                                   ctx->stream, d_cand0, d_n0, 0ull, 0u, d_hist0);
-            else
-                hipLaunchKernelGGL(k_cand_hist, dim3(hgrid), dim3(256), 0,
-                                   ctx->stream, d_cand0, d_n0, 0ull, 0u, d_hist0);
-            HIP_CHECK(hipMemcpyAsync(hist0, d_hist0, TOPK_BINS * 4,
-                                     hipMemcpyDeviceToHost, ctx->stream));
-            hist0_valid = true;
-        }
-
-        // ---- download counts (into pinned staging: no pageable D2H)
-        ctx->h_counts.ensure(size_t(n_tiles) * 4 + 64);
-        uint32_t* tile_counts = (uint32_t*)ctx->h_counts.p;
-        uint32_t* pc = (uint32_t*)(ctx->h_counts.p + size_t(n_tiles) * 4);
-        HIP_CHECK(hipMemcpyAsync(tile_counts, ctx->d_results.p + r_tile_counts,
-                                 size_t(n_tiles) * 4, hipMemcpyDeviceToHost,
-                                 ctx->stream));
-        if (collect)
-            HIP_CHECK(hipMemcpyAsync(pc, ctx->d_results.p + r_cand_count, 4,
-                                     hipMemcpyDeviceToHost, ctx->stream));
-        if (do_aggs && ap.out_bytes) {
-            // aggregation results ride the same async batch + sync (a
-            // blocking copy after hit building cost ~40 us per split)
-            ctx->h_agg.ensure(ap.out_bytes + 64);
-            HIP_CHECK(hipMemcpyAsync(ctx->h_agg.p, ctx->d_results.p + r_agg,
-                                     ap.out_bytes, hipMemcpyDeviceToHost,
-                                     ctx->stream));
-        }
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        uint32_t cand_n = collect ? *pc : 0;
-        mark("main+pass0+sync");
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-        record_kernel_time(ctx, kname, ms);
-        for (uint32_t i = 0; i < n_tiles; ++i) matched += tile_counts[i];
-        if (collect) {
-            ++(prune_k ? ctx->topk_pruned : ctx->topk_unpruned);
-            ctx->topk_last_emitted = cand_n;
-            ctx->topk_last_matched = matched;
-        }
-
-        // ---- top-K selection over candidates (device histogram refinement
-        // + host exact sort of the survivors; top_k_collector.rs semantics)
-        if (collect && cand_n > 0) {
-            uint32_t rw = wide ? 2 : 1;  // u64 words per candidate record
-            uint64_t* d_cand = (uint64_t*)(ctx->d_results.p + r_cand);
-            uint32_t* d_hist = (uint32_t*)(ctx->d_results.p + r_hist);
-            uint32_t* d_scount = (uint32_t*)(ctx->d_results.p + r_cand_count) + 1;
-            // search_after: pre-compact to the cursor's primary-value band
-            // (inclusive upper bound in device-key space; ties and the
-            // (v2, split, seg, doc) chain are settled by the exact host
-            // filter at hit building, with a growing-K retry on shortfall)
-            if (after) {
-                uint64_t ceil_key = ~0ull;
-                const SortKey& k1 = ck1.key;  // converted to the field domain
-                if (wide) {
-                    if (!k1.has) ceil_key = 0;  // cursor in the None region
-                    else {
-                        uint64_t S = k1.key;
-                        if (!specs.empty() && specs[0].comp == SortSpec::SCORE) {
-                            uint32_t kh = f32_sortable_h(float(u64_to_f64(S)));
-                            S = (uint64_t(kh) << 32) | 0xFFFFFFFFull;
-                        } else if (!specs.empty() && specs[0].ff &&
-                                   specs[0].ff->type == FastFieldView::DATETIME) {
-                            int64_t ns = u64_to_i64(S);  // cursor carries ns
-                            int64_t ms = ns / 1000000 - ((ns % 1000000) < 0 ? 1 : 0);
-                            S = i64_to_u64(ms);
-                        }
-                        // I64/F64: same u64 map as the device key;
-                        // U64/STR ord: identity
-                        ceil_key = (order1 == 0) ? ~S : S;
-                    }
-                } else {
-                    uint32_t kh = 0;
-                    if (fq.scoring && k1.has)
-                        kh = f32_sortable_h(float(u64_to_f64(k1.key)));
-                    bool nasc = !specs.empty() &&
-                                specs[0].comp != SortSpec::DOC_ID && order1 == 0;
-                    if (nasc) kh = ~kh;
-                    ceil_key = (uint64_t(kh) << 32) | 0xFFFFFFFFull;
-                }
-                qw_ensure_acct(ctx, ctx->d_cand2, size_t(cand_n) * 8 * rw + 16);
-                uint32_t* d_c2n = (uint32_t*)(ctx->d_results.p + r_cand_count) + 2;
-                HIP_CHECK(hipMemsetAsync(d_c2n, 0, 4, ctx->stream));
-                uint32_t pgrid = std::min<uint32_t>(2048, (cand_n + 255) / 256);
-                if (wide)
-                    hipLaunchKernelGGL(k_cand_compact_w, dim3(pgrid), dim3(256), 0,
-                                       ctx->stream, d_cand, cand_n, 0ull, ceil_key,
-                                       (uint64_t*)ctx->d_cand2.p, d_c2n, cand_n);
-                else
-                    hipLaunchKernelGGL(k_cand_compact, dim3(pgrid), dim3(256), 0,
-                                       ctx->stream, d_cand, cand_n, 0ull, ceil_key,
-                                       (uint64_t*)ctx->d_cand2.p, d_c2n, cand_n);
-                uint32_t n2 = 0;
-                HIP_CHECK(hipMemcpyAsync(&n2, d_c2n, 4, hipMemcpyDeviceToHost,
-                                         ctx->stream));
-                HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                d_cand = (uint64_t*)ctx->d_cand2.p;
-                cand_n = n2;
-            }
-        }
-        if (collect && cand_n > 0) {
-            uint64_t* d_cand = after ? (uint64_t*)ctx->d_cand2.p
-                                     : (uint64_t*)(ctx->d_results.p + r_cand);
-            uint32_t* d_hist = (uint32_t*)(ctx->d_results.p + r_hist);
-            uint32_t* d_scount = (uint32_t*)(ctx->d_results.p + r_cand_count) + 1;
-            uint32_t rw = wide ? 2 : 1;  // u64 words per candidate record
-            sel_band_n = cand_n;
-            // capture the block-local selection state BY VALUE: the lambda is
-            // re-invoked by the search_after growing-K retry (below) after
-            // this block's scope has ended
-            rerun_select = [&, d_cand, rw, cand_n, d_hist, d_scount,
-                            hist0_valid](uint64_t Kwant) {
-            uint64_t K = std::min<uint64_t>(Kwant, cand_n);
-            uint64_t prefix = 0;
-            uint32_t prefix_bits = 0;
-            uint64_t survivors = cand_n, above = 0, Krem = K;
-            uint64_t floor_key = 0;
-            std::vector<uint32_t> hist(TOPK_BINS);
-            HIP_CHECK(hipEventRecord(ctx->ev_start, ctx->stream));
-            while (true) {
-                // refine until the band is small: the D2H + host sort of
-                // the survivors is on the critical path (a 65k-u64 band
-                // cost ~90 us at K=1000; one more 4096-bin pass is ~20 us)
-                if (survivors <= std::max<uint64_t>(4 * K, 16384) || prefix_bits >= 48) {
-                    if (prefix_bits == 0) floor_key = 0;
-                    break;
-                }
-                if (prefix_bits == 0 && hist0_valid) {
-                    memcpy(hist.data(), hist0,
-                           TOPK_BINS * 4);  // prefetched with the main sync
-                } else {
-                    HIP_CHECK(hipMemsetAsync(d_hist, 0, TOPK_BINS * 4, ctx->stream));
-                    // grid small enough that the per-WG 4096-bin LDS flush
-                    // (global atomics ∝ grid) stays cheap, yet fills the chip
-                    uint32_t hgrid = std::min<uint32_t>(512, (cand_n + 4095) / 4096);
-                    uint32_t* d_n = after
-                        ? (uint32_t*)(ctx->d_results.p + r_cand_count) + 2
-                        : (uint32_t*)(ctx->d_results.p + r_cand_count);
-                    if (wide)
-                        hipLaunchKernelGGL(k_cand_hist_w, dim3(hgrid), dim3(256), 0,
-                                           ctx->stream, d_cand, d_n, prefix,
-                                           prefix_bits, d_hist);
-                    else
-                        hipLaunchKernelGGL(k_cand_hist, dim3(hgrid), dim3(256), 0,
-                                           ctx->stream, d_cand, d_n, prefix,
-                                           prefix_bits, d_hist);
-                    HIP_CHECK(hipMemcpyAsync(hist.data(), d_hist, TOPK_BINS * 4,
-                                             hipMemcpyDeviceToHost, ctx->stream));
-                    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                }
-                uint64_t cum = 0;
-                int b = TOPK_BINS - 1;
-                for (; b >= 0; --b) {
-                    if (cum + hist[b] >= Krem) break;
-                    cum += hist[b];
-                }
-                if (b < 0) b = 0;
-                uint32_t shift = 64 - prefix_bits - 12;
-                floor_key = (prefix_bits ? (prefix << (64 - prefix_bits)) : 0) |
-                            (uint64_t(uint32_t(b)) << shift);
-                above += cum;
-                survivors = above + hist[b];
-                Krem = Krem - cum;
-                prefix = (prefix << 12) | uint64_t(uint32_t(b));
-                prefix_bits += 12;
-            }
-            // #keys >= floor_key is known EXACTLY from the histogram walk, so
-            // no round trip for the compact count: one async D2H of survivors
-            qw_ensure_acct(ctx, ctx->d_survivors, survivors * 8 * rw + 16);
-            HIP_CHECK(hipMemsetAsync(d_scount, 0, 4, ctx->stream));
-            uint32_t cgrid = std::min<uint32_t>(2048, (cand_n + 255) / 256);
-            if (wide)
-                hipLaunchKernelGGL(k_cand_compact_w, dim3(cgrid), dim3(256), 0,
-                                   ctx->stream, d_cand, cand_n, floor_key, ~0ull,
-                                   (uint64_t*)ctx->d_survivors.p, d_scount,
-                                   uint32_t(survivors));
-            else
-                hipLaunchKernelGGL(k_cand_compact, dim3(cgrid), dim3(256), 0,
-                                   ctx->stream, d_cand, cand_n, floor_key, ~0ull,
-                                   (uint64_t*)ctx->d_survivors.p, d_scount,
-                                   uint32_t(survivors));
-            top_keys.resize(survivors * rw);
-            ctx->h_topk.ensure(survivors * 8 * rw + 16);
-            HIP_CHECK(hipMemcpyAsync(ctx->h_topk.p, ctx->d_survivors.p,
-                                     survivors * 8 * rw, hipMemcpyDeviceToHost,
-                                     ctx->stream));
-            HIP_CHECK(hipEventRecord(ctx->ev_stop, ctx->stream));
-            HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            memcpy(top_keys.data(), ctx->h_topk.p, survivors * 8 * rw);
-            float tms = 0;
-            HIP_CHECK(hipEventElapsedTime(&tms, ctx->ev_start, ctx->ev_stop));
-            record_kernel_time(ctx, "topk_select", tms);
-            if (!wide) {
-                std::sort(top_keys.begin(), top_keys.end(),
-                          std::greater<uint64_t>());
-                if (top_keys.size() > K && !after) top_keys.resize(K);
-            }
-            };  // rerun_select
-            sel_kwant = std::min<uint64_t>(
-                leaf_max_hits + (after ? 1024 : 0), cand_n);
-            rerun_select(sel_kwant);
-            mark("topk_select");
-        }
-    } else {
-        matched = sv.num_docs;  // pure match_all, no aggs
-    }
-    if (pure_match_all) matched = sv.num_docs;
-
-    out.num_hits = matched;
-
-    // ---- build PartialHits
-    auto mk_hit = [&](uint32_t doc, float score) {
-        pb::PartialHit h;
-        h.split_id = sv.split_id;
-        h.segment_ord = sv.segment_ord;
-        h.doc_id = doc;
-        if (!specs.empty()) h.sort_value = sort_value_of(specs[0], doc, score);
-        if (specs.size() > 1) h.sort_value2 = sort_value_of(specs[1], doc, score);
-        return h;
-    };
-    if (leaf_max_hits > 0) {
-        if (trivial_hits) {
-            // hits enumerable without the kernel: doc-id order (desc default)
-            uint64_t k = std::min<uint64_t>(leaf_max_hits, sv.num_docs);
-            for (uint64_t i = 0; i < k; ++i) {
-                uint32_t doc = order1 == 1 ? uint32_t(sv.num_docs - 1 - i)
-                                           : uint32_t(i);
-                out.hits.push_back(mk_hit(doc, 0.f));
+                // MIXED columns store f64-monotonic u64 keys: ascending
+                // u64 order IS the numeric order -> device treats them
+                // like a u64 column
+                q.sort_src = f->type == FastFieldView::U64    ? 2
+                             : f->type == FastFieldView::MIXED ? 2
+                             : f->type == FastFieldView::F64  ? 4
+                                                              : 3;
+                q.sort_width = 8;
             }
         } else {
-            // build hits from the survivors; with search_after, the exact
-            // cursor filter runs before truncation and the selection widens
-            // (growing K) until the page is full or the band is exhausted
-            for (;;) {
-                out.hits.clear();
-                out.hits.reserve(top_keys.size() / (wide ? 2 : 1));
-                if (wide) {
-                    // survivors carry (selection key, score|doc); the exact
-                    // reference order ((sort_value, sort_value2, GlobalDocId),
-                    // sorting.md:14-26) is re-established over the survivors
-                    size_t n = top_keys.size() / 2;
-                    out.hits.reserve(n);
-                    for (size_t i = 0; i < n; ++i) {
-                        uint64_t aux = top_keys[2 * i + 1];
-                        uint32_t doc = uint32_t(aux);
-                        float score = 0.f;
-                        if (fq.scoring) {
-                            uint32_t b = uint32_t(aux >> 32);
-                            memcpy(&score, &b, 4);
-                        }
-                        out.hits.push_back(mk_hit(doc, score));
-                    }
-                } else {
-                    bool asc = !specs.empty() && order1 == 0;
-                    for (uint64_t key : top_keys) {
-                        uint32_t kh = uint32_t(key >> 32), kl = uint32_t(key);
-                        if (asc) {
-                            kh = ~kh;
-                            kl = ~kl;
-                        }
-                        float score = 0.f;
-                        if (fq.scoring) {
-                            uint32_t b =
-                                (kh & 0x80000000u) ? (kh & ~0x80000000u) : ~kh;
-                            memcpy(&score, &b, 4);
-                        }
-                        out.hits.push_back(mk_hit(kl, score));
-                    }
-                }
-                if (after) {
-                    const pb::PartialHit& c = *after;
-                    out.hits.erase(
-                        std::remove_if(out.hits.begin(), out.hits.end(),
-                                       [&](const pb::PartialHit& h) {
-                                           return !after_cursor(
-                                               h, c, ck1, ck2, order1, order2,
-                                               !specs.empty() &&
-                                                   kind_of(specs[0]) ==
-                                                       SortFieldKind::MIXED,
-                                               specs.size() > 1 &&
-                                                   kind_of(specs[1]) ==
-                                                       SortFieldKind::MIXED);
-                                       }),
-                        out.hits.end());
-                }
-                auto cmp = [&](const pb::PartialHit& a, const pb::PartialHit& b) {
-                    return hit_before(a, b, order1, order2);
-                };
-                size_t k = std::min<size_t>(leaf_max_hits, out.hits.size());
-                std::partial_sort(out.hits.begin(), out.hits.begin() + k,
-                                  out.hits.end(), cmp);
-                out.hits.resize(k);
-                if (!after || !rerun_select ||
-                    out.hits.size() >= std::min<uint64_t>(leaf_max_hits, sel_band_n) ||
-                    sel_kwant >= sel_band_n)
-                    break;
-                sel_kwant = std::min<uint64_t>(sel_band_n, sel_kwant * 8);
-                rerun_select(sel_kwant);
-            }
+            q.sort_src = 0;  // unknown field: every key is None
         }
     }
-    mark("build_hits");
+    q.terms_off = L.off_terms;
+    q.preds_off = L.off_preds;
+    q.aggs_off = L.off_aggs;
+    q.ktabs_off = L.off_ktabs;
+    // LDS staging of fieldnorms + K tables for the scoring decode path
+    // (kernels.hip): enabled when every scored term's norms live in ONE
+    // section (single-field queries — the flagship shape) and the K
+    // tables fit the LDS budget. QW_NO_LDS_NORMS / QW_NO_LDS_KTAB are
+    // perf-experiment kill switches.
+    if (fq.scoring) {
+        // measured on MI355X at the 100M flagship: norms staging LOSES
+        // (the +8KB LDS drops occupancy 4->3 WGs/CU while the norm
+        // gathers already hit L2 — union covers ~25% of docs, ~16 hits
+        // per cacheline); ktab staging is noise. Both stay available as
+        // opt-in experiment switches (gpurun_out/r02_exp_variants.log).
+        static const bool want_norms = getenv("QW_LDS_NORMS") != nullptr;
+        static const bool want_ktab = getenv("QW_LDS_KTAB") != nullptr;
+        uint64_t common = 0;
+        bool uniform = true;
+        for (const TermDev& t : tt.terms)
+            if (t.norms_off) {
+                if (!common) common = t.norms_off;
+                else if (common != t.norms_off) uniform = false;
+            }
+        q.norms_stage_off = (want_norms && uniform) ? common : 0;
+        q.n_ktabs = (want_ktab && fq.ktab_fields.size() <= KTAB_LDS_MAX)
+                        ? uint32_t(fq.ktab_fields.size())
+                        : 0;
+    }
+    q.tile_counts_off = L.r_tile_counts;
+    q.cand_count_off = L.r_cand_count;
+    q.cand_off = L.r_cand;
+    q.cand_cap = L.cand_cap;
+    q.hist_off = L.r_hist;
+    // prune candidates in the tile kernel: narrow records, small K, no
+    // cursor (the cursor band is cut out of ALL candidates afterwards),
+    // and a real candidate array
+    if (collect && !sp.wide && !sp.after && L.cand_cap > 0 && leaf_max_hits >= 1 &&
+        leaf_max_hits <= TOPK_PRUNE_MAX_K && ctx->topk_prune)
+        q.prune_k = uint32_t(leaf_max_hits);
 
-    // ---- aggregation download + assembly (QAGG1 intermediate)
-    if (do_aggs) {
-        // downloaded asynchronously with the counts batch above (pinned)
+    tl.kname = !fq.terms.empty() ? "union_bm25"
+               : do_aggs         ? "column_agg"
+                                 : "range_filter";
+    uint32_t n_should = uint32_t(tt.terms.size()) - tt.n_must - tt.n_must_not;
+    tl.ns = n_should > 0 || (fq.scoring && !tt.terms.empty());
+    tl.nb = tt.n_must > 0 || tt.n_must_not > 0;
+    tl.na = do_aggs && !ap.devs.empty();
+    // agg workloads: capped grid so the once-per-workgroup LDS flush
+    // stays cheap (each WG owns several tiles). For PURE column scans
+    // (no posting decode) the grid also scales DOWN with the split
+    // size — the flush costs grid x buckets global atomics regardless
+    // of docs, which dominated small splits (256 WGs x 4 waves still
+    // fill the chip's 1024 resident-wave slots). Decode-carrying
+    // kernels keep the wide grid: fewer WGs serialize the per-tile
+    // decode loops and cost more than the flush saves (measured,
+    // config5 ablation).
+    tl.grid = n_tiles;
+    if (tl.na)
+        tl.grid = fq.terms.empty()
+                      ? std::min<uint32_t>(
+                            {n_tiles, 2048u, std::max<uint32_t>(256u, n_tiles / 8)})
+                      : std::min<uint32_t>(n_tiles, 2048u);
+    // straight-line agg path (kernels.hip): histo[0] int_fast LDS
+    // non-nullable no-subs (+ optional terms[1] LDS non-nullable)
+    if (tl.na && !ap.devs.empty() && ap.devs[0].kind == AGGD_HISTO &&
+        ap.devs[0].lds_slot == 0 && ap.devs[0].int_fast &&
+        ap.devs[0].n_sub == 0 && ap.devs[0].nulls_off == 0 &&
+        ap.devs.size() <= 2 &&
+        (ap.devs.size() < 2 ||
+         (ap.devs[1].kind == AGGD_TERMS && ap.devs[1].lds_slot == 1 &&
+          ap.devs[1].nulls_off == 0 && ap.devs[1].offsets_off == 0 &&
+          ap.devs[1].n_buckets > 0)))
+        q.agg_fast = 1;
+    // terms-only straight-line path (config5's shape): one LDS terms
+    // agg, non-nullable single-valued ord column, no subs
+    if (tl.na && ap.devs.size() == 1 && ap.devs[0].kind == AGGD_TERMS &&
+        ap.devs[0].lds_slot == 1 && ap.devs[0].n_sub == 0 &&
+        ap.devs[0].nulls_off == 0 && ap.devs[0].offsets_off == 0 &&
+        ap.devs[0].n_buckets > 0)
+        q.agg_fast = 1;
+    static const bool agg_nt = getenv("QW_AGG_NT") != nullptr;
+    q.agg_nt = agg_nt ? 1 : 0;
+    static const bool nt_decode = getenv("QW_NT_DECODE") != nullptr;
+    q.nt_decode = nt_decode ? 1 : 0;
+    return tl;
+}
+
+// the wide/narrow choice of each selection kernel, once
+static void launch_cand_hist(bool wide, uint32_t grid, hipStream_t stream,
+                             const uint64_t* cand, const uint32_t* n_ptr,
+                             uint64_t prefix, uint32_t prefix_bits,
+                             uint32_t* hist) {
+    if (wide)
+        hipLaunchKernelGGL(k_cand_hist_w, dim3(grid), dim3(256), 0, stream, cand,
+                           n_ptr, prefix, prefix_bits, hist);
+    else
+        hipLaunchKernelGGL(k_cand_hist, dim3(grid), dim3(256), 0, stream, cand,
+                           n_ptr, prefix, prefix_bits, hist);
+}
+static void launch_cand_compact(bool wide, uint32_t grid, hipStream_t stream,
+                                const uint64_t* cand, uint32_t n,
+                                uint64_t floor_key, uint64_t ceil_key,
+                                uint64_t* out, uint32_t* out_count, uint32_t cap) {
+    if (wide)
+        hipLaunchKernelGGL(k_cand_compact_w, dim3(grid), dim3(256), 0, stream,
+                           cand, n, floor_key, ceil_key, out, out_count, cap);
+    else
+        hipLaunchKernelGGL(k_cand_compact, dim3(grid), dim3(256), 0, stream, cand,
+                           n, floor_key, ceil_key, out, out_count, cap);
+}
+
+// inclusive upper bound, in device-key space, of the search_after cursor's
+// primary-value band (ties and the (v2, split, seg, doc) chain are settled
+// by the exact host filter at hit building)
+static uint64_t cursor_ceil_key(const SortPlan& sp, bool fq_scoring) {
+    const SortKey& k1 = sp.ck1.key;  // converted to the field domain
+    if (sp.wide) {
+        if (!k1.has) return 0;  // cursor in the None region
+        uint64_t S = k1.key;
+        if (sp.specs[0].comp == SortSpec::SCORE) {
+            uint32_t kh = f32_sortable_h(float(u64_to_f64(S)));
+            S = (uint64_t(kh) << 32) | 0xFFFFFFFFull;
+        } else if (sp.specs[0].ff &&
+                   sp.specs[0].ff->type == FastFieldView::DATETIME) {
+            int64_t ns = u64_to_i64(S);  // cursor carries ns
+            int64_t ms = ns / 1000000 - ((ns % 1000000) < 0 ? 1 : 0);
+            S = i64_to_u64(ms);
+        }
+        // I64/F64: same u64 map as the device key; U64/STR ord: identity
+        return sp.order1 == 0 ? ~S : S;
+    }
+    uint32_t kh = 0;
+    if (fq_scoring && k1.has) kh = f32_sortable_h(float(u64_to_f64(k1.key)));
+    if (sp.sort_asc()) kh = ~kh;
+    return (uint64_t(kh) << 32) | 0xFFFFFFFFull;
+}
+
+// top-K selection over the candidate records (device histogram refinement
+// + host exact sort of the survivors; top_k_collector.rs semantics). Owns
+// the state the growing-K retry of build_hits steers.
+struct TopkSelector {
+    qw_ctx* ctx;
+    bool wide, after;        // after: an effective search_after cursor
+    uint32_t rw;             // u64 words per candidate record
+    uint64_t leaf_max_hits;
+    uint64_t* d_cand = nullptr;  // records selected from: all candidates,
+                                 // or the cursor band once compacted
+    uint32_t* d_n = nullptr;     // device-side count of those records
+    uint32_t* d_hist = nullptr;
+    // cand_count header words (gpu_types.h)
+    uint32_t *d_candidates = nullptr, *d_survivors = nullptr, *d_band = nullptr;
+    // prefetched selection pass-0 histogram, in pinned staging (async D2H
+    // to pageable memory degrades to a blocking staged copy)
+    uint32_t* hist0;
+    bool hist0_valid = false;
+    uint64_t band_n = 0;  // records in d_cand
+    uint64_t kwant = 0;   // K of the last select()
+    std::vector<uint64_t> top_keys;  // survivors (narrow: sorted best-first)
+
+    TopkSelector(qw_ctx* c, bool wide_, bool after_, uint64_t leaf_max_hits_)
+        : ctx(c), wide(wide_), after(after_), rw(wide_ ? 2 : 1),
+          leaf_max_hits(leaf_max_hits_) {
+        ctx->h_surv.ensure(TOPK_BINS * 4);
+        hist0 = (uint32_t*)ctx->h_surv.p;
+    }
+
+    // ctx->d_results must be sized for L already
+    void attach(const ScratchLayout& L) {
+        uint8_t* hdr = ctx->d_results.p + L.r_cand_count;
+        d_cand = (uint64_t*)(ctx->d_results.p + L.r_cand);
+        d_hist = (uint32_t*)(ctx->d_results.p + L.r_hist);
+        d_candidates = cand_hdr_candidates(hdr);
+        d_survivors = cand_hdr_survivors(hdr);
+        d_band = cand_hdr_cursor_band(hdr);
+        d_n = d_candidates;
+    }
+
+    // enqueue histogram pass 0 behind the main kernel (count read
+    // device-side) so its result arrives with the same synchronize
+    // (kept when pruning: the 100M flagship still emits ~130k records,
+    // above the 16384 no-refinement threshold, and a pass over that few
+    // costs far less than the extra round trip select() would need)
+    void enqueue_pass0(uint32_t num_docs) {
+        HIP_CHECK(hipMemsetAsync(d_hist, 0, TOPK_BINS * 4, ctx->stream));
+        // candidate count is device-side only at this point: size the
+        // grid for the worst case (every doc a candidate)
+        uint32_t hgrid = std::min<uint32_t>(512, (num_docs + 4095) / 4096);
+        launch_cand_hist(wide, hgrid, ctx->stream, d_cand, d_candidates, 0ull, 0u,
+                         d_hist);
+        HIP_CHECK(hipMemcpyAsync(hist0, d_hist, TOPK_BINS * 4,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+        hist0_valid = true;
+    }
+
+    // search_after: pre-compact the band_n candidates to the cursor's
+    // primary-value band; selection then runs over the band only
+    void compact_cursor_band(uint64_t ceil_key) {
+        uint32_t cand_n = uint32_t(band_n);
+        qw_ensure_acct(ctx, ctx->d_cand2, size_t(cand_n) * 8 * rw + 16);
+        HIP_CHECK(hipMemsetAsync(d_band, 0, 4, ctx->stream));
+        uint32_t pgrid = std::min<uint32_t>(2048, (cand_n + 255) / 256);
+        launch_cand_compact(wide, pgrid, ctx->stream, d_cand, cand_n, 0ull,
+                            ceil_key, (uint64_t*)ctx->d_cand2.p, d_band, cand_n);
+        uint32_t n2 = 0;
+        HIP_CHECK(hipMemcpyAsync(&n2, d_band, 4, hipMemcpyDeviceToHost,
+                                 ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        d_cand = (uint64_t*)ctx->d_cand2.p;
+        d_n = d_band;
+        band_n = n2;
+    }
+
+    // fills top_keys with every record whose key is >= the K-th best key
+    void select(uint64_t Kwant) {
+        kwant = Kwant;
+        const uint32_t cand_n = uint32_t(band_n);
+        uint64_t K = std::min<uint64_t>(Kwant, cand_n);
+        uint64_t prefix = 0;
+        uint32_t prefix_bits = 0;
+        uint64_t survivors = cand_n, above = 0, Krem = K;
+        uint64_t floor_key = 0;
+        std::vector<uint32_t> hist(TOPK_BINS);
+        HIP_CHECK(hipEventRecord(ctx->ev_start, ctx->stream));
+        while (true) {
+            // refine until the band is small: the D2H + host sort of
+            // the survivors is on the critical path (a 65k-u64 band
+            // cost ~90 us at K=1000; one more 4096-bin pass is ~20 us)
+            if (survivors <= std::max<uint64_t>(4 * K, 16384) || prefix_bits >= 48) {
+                if (prefix_bits == 0) floor_key = 0;
+                break;
+            }
+            if (prefix_bits == 0 && hist0_valid) {
+                memcpy(hist.data(), hist0,
+                       TOPK_BINS * 4);  // prefetched with the main sync
+            } else {
+                HIP_CHECK(hipMemsetAsync(d_hist, 0, TOPK_BINS * 4, ctx->stream));
+                // grid small enough that the per-WG 4096-bin LDS flush
+                // (global atomics ∝ grid) stays cheap, yet fills the chip
+                uint32_t hgrid = std::min<uint32_t>(512, (cand_n + 4095) / 4096);
+                launch_cand_hist(wide, hgrid, ctx->stream, d_cand, d_n, prefix,
+                                 prefix_bits, d_hist);
+                HIP_CHECK(hipMemcpyAsync(hist.data(), d_hist, TOPK_BINS * 4,
+                                         hipMemcpyDeviceToHost, ctx->stream));
+                HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            }
+            uint64_t cum = 0;
+            int b = TOPK_BINS - 1;
+            for (; b >= 0; --b) {
+                if (cum + hist[b] >= Krem) break;
+                cum += hist[b];
+            }
+            if (b < 0) b = 0;
+            uint32_t shift = 64 - prefix_bits - 12;
+            floor_key = (prefix_bits ? (prefix << (64 - prefix_bits)) : 0) |
+                        (uint64_t(uint32_t(b)) << shift);
+            above += cum;
+            survivors = above + hist[b];
+            Krem = Krem - cum;
+            prefix = (prefix << 12) | uint64_t(uint32_t(b));
+            prefix_bits += 12;
+        }
+        // #keys >= floor_key is known EXACTLY from the histogram walk, so
+        // no round trip for the compact count: one async D2H of survivors
+        qw_ensure_acct(ctx, ctx->d_survivors, survivors * 8 * rw + 16);
+        HIP_CHECK(hipMemsetAsync(d_survivors, 0, 4, ctx->stream));
+        uint32_t cgrid = std::min<uint32_t>(2048, (cand_n + 255) / 256);
+        launch_cand_compact(wide, cgrid, ctx->stream, d_cand, cand_n, floor_key,
+                            ~0ull, (uint64_t*)ctx->d_survivors.p, d_survivors,
+                            uint32_t(survivors));
+        top_keys.resize(survivors * rw);
+        ctx->h_topk.ensure(survivors * 8 * rw + 16);
+        HIP_CHECK(hipMemcpyAsync(ctx->h_topk.p, ctx->d_survivors.p,
+                                 survivors * 8 * rw, hipMemcpyDeviceToHost,
+                                 ctx->stream));
+        HIP_CHECK(hipEventRecord(ctx->ev_stop, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        memcpy(top_keys.data(), ctx->h_topk.p, survivors * 8 * rw);
+        float tms = 0;
+        HIP_CHECK(hipEventElapsedTime(&tms, ctx->ev_start, ctx->ev_stop));
+        record_kernel_time(ctx, "topk_select", tms);
+        if (!wide) {
+            std::sort(top_keys.begin(), top_keys.end(), std::greater<uint64_t>());
+            if (top_keys.size() > K && !after) top_keys.resize(K);
+        }
+    }
+
+    // search_after shortfall: the exact cursor filter left fewer than a page
+    // of n_hits hits. Re-selects with K x8 and returns true, or returns
+    // false when the page is full or the band is exhausted.
+    bool grow(size_t n_hits) {
+        if (!after || band_n == 0 ||
+            n_hits >= std::min<uint64_t>(leaf_max_hits, band_n) || kwant >= band_n)
+            return false;
+        select(std::min<uint64_t>(band_n, kwant * 8));
+        return true;
+    }
+};
+
+struct TileRun {
+    uint64_t matched = 0;  // sum of the tile counts
+    uint32_t cand_n = 0;   // candidate records written
+};
+
+// query scratch upload + results reset; enqueued before fill_query_dev so
+// that host work overlaps the copies
+static void enqueue_uploads(qw_ctx* ctx, const ScratchLayout& L,
+                            const AggPlan& ap, bool do_aggs) {
+    HIP_CHECK(hipMemcpyAsync(ctx->d_scratch.p, ctx->h_scratch.p, L.scratch_bytes,
+                             hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipMemsetAsync(ctx->d_results.p, 0, L.r_agg, ctx->stream));
+    if (do_aggs && ap.out_bytes)
+        HIP_CHECK(hipMemcpyAsync(ctx->d_results.p + L.r_agg, ap.init.data(),
+                                 ap.out_bytes, hipMemcpyHostToDevice, ctx->stream));
+}
+
+// the tile kernel, selection pass 0 and every download that rides the same
+// synchronize
+static TileRun run_leaf_tile(qw_ctx* ctx, const SplitView& sv,
+                             const TileLaunch& tl, const ScratchLayout& L,
+                             const AggPlan& ap, bool collect, bool do_aggs,
+                             TopkSelector& sel, StageTimer& timer) {
+    const uint32_t n_tiles = tl.q.n_tiles;
+    HIP_CHECK(hipEventRecord(ctx->ev_start, ctx->stream));
+    launch_leaf_tile(tl.ns, tl.nb, tl.na, collect, dim3(tl.grid), ctx->stream,
+                     tl.q, 0u, n_tiles, 1u);
+    HIP_CHECK(hipEventRecord(ctx->ev_stop, ctx->stream));
+    HIP_CHECK(hipGetLastError());
+    if (collect && !sel.after) sel.enqueue_pass0(sv.num_docs);
+
+    // ---- download counts (into pinned staging: no pageable D2H)
+    ctx->h_counts.ensure(size_t(n_tiles) * 4 + 64);
+    uint32_t* tile_counts = (uint32_t*)ctx->h_counts.p;
+    uint32_t* pc = (uint32_t*)(ctx->h_counts.p + size_t(n_tiles) * 4);
+    HIP_CHECK(hipMemcpyAsync(tile_counts, ctx->d_results.p + L.r_tile_counts,
+                             size_t(n_tiles) * 4, hipMemcpyDeviceToHost,
+                             ctx->stream));
+    if (collect)
+        HIP_CHECK(hipMemcpyAsync(pc, ctx->d_results.p + L.r_cand_count, 4,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+    if (do_aggs && ap.out_bytes) {
+        // aggregation results ride the same async batch + sync (a
+        // blocking copy after hit building cost ~40 us per split)
         ctx->h_agg.ensure(ap.out_bytes + 64);
-        const uint8_t* agg_out_p = ctx->h_agg.p;
-        for (size_t i = 0; i < ap.defs.size(); ++i) {
-            const AggDef& d = ap.defs[i];
-            const AggDev& a = ap.devs[i];
-            const FastFieldView* f = ap.fields[i];
-            AggResult r;
-            r.name = d.name;
-            for (auto& s : d.sub) r.sub_names.push_back(s.name);
-            const uint8_t* base = agg_out_p + (a.counts_out - r_agg);
-            const uint64_t* counts = (const uint64_t*)base;
-            if (d.kind == AggDef::TERMS || d.kind == AggDef::CARDINALITY) {
-                r.kind = 3;
-                if (a.n_buckets) {
-                    if (a.nulls_off || a.offsets_off) {
-                        uint64_t m = 0;
-                        memcpy(&m, agg_out_p + (a.matched_out - r_agg), 8);
-                        r.terms_matched_docs = m;
-                    } else {
-                        // non-nullable column: every matched doc has a value
-                        r.terms_matched_docs = matched;
-                    }
-                    if (a.kind == AGGD_TERMS_NUM) {
-                        r.key_kind = f->type == FastFieldView::U64   ? 1
-                                     : f->type == FastFieldView::F64 ? 3
-                                                                     : 2;
-                        uint32_t slots = (a.n_buckets - 2) >> 1;
-                        if (counts[2 * uint64_t(slots) + 1])
-                            throw std::runtime_error(
-                                "numeric terms hash table overflow");
-                        for (uint64_t s2 = 0; s2 < slots; ++s2) {
-                            uint64_t key = counts[2 * s2], c = counts[2 * s2 + 1];
-                            if (key != ~0ull && c)
-                                r.term_counts.emplace_back(num_term_key(key), c);
-                        }
-                        if (uint64_t sc2 = counts[2 * uint64_t(slots)])
-                            r.term_counts.emplace_back(num_term_key(~0ull), sc2);
-                        std::sort(r.term_counts.begin(), r.term_counts.end());
-                    } else {
-                        const uint8_t* subs =
-                            agg_out_p + (a.sub_out - r_agg);
-                        for (uint32_t o = 0; o < a.n_buckets; ++o)
-                            if (counts[o]) {
-                                r.term_counts.emplace_back(f->dict_entry(o),
-                                                           counts[o]);
-                                if (a.n_sub) {
-                                    std::vector<StatsPayload> ts(d.sub.size());
-                                    for (uint32_t s = 0; s < a.n_sub; ++s) {
-                                        const uint8_t* slot =
-                                            subs +
-                                            (uint64_t(o) * a.n_sub + s) * 40;
-                                        StatsPayload sp2;
-                                        uint64_t mn, mx;
-                                        memcpy(&sp2.count, slot, 8);
-                                        memcpy(&sp2.sum, slot + 8, 8);
-                                        memcpy(&mn, slot + 16, 8);
-                                        memcpy(&mx, slot + 24, 8);
-                                        memcpy(&sp2.sum_sq, slot + 32, 8);
-                                        if (sp2.count) {
-                                            sp2.min = u64_to_f64(mn);
-                                            sp2.max = u64_to_f64(mx);
-                                        }
-                                        ts[s] = sp2;
-                                    }
-                                    r.term_subs.push_back(std::move(ts));
-                                }
-                            }
-                    }
-                    if (d.kind == AggDef::TERMS)
-                        truncate_terms_split(
-                            r, effective_split_size(d.size, d.split_size),
-                            d.order_target, d.order_asc, &d.sub);
+        HIP_CHECK(hipMemcpyAsync(ctx->h_agg.p, ctx->d_results.p + L.r_agg,
+                                 ap.out_bytes, hipMemcpyDeviceToHost,
+                                 ctx->stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    TileRun run;
+    run.cand_n = collect ? *pc : 0;
+    timer.mark("main+pass0+sync");
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+    record_kernel_time(ctx, tl.kname, ms);
+    for (uint32_t i = 0; i < n_tiles; ++i) run.matched += tile_counts[i];
+    if (collect) {
+        ++(tl.q.prune_k ? ctx->topk_pruned : ctx->topk_unpruned);
+        ctx->topk_last_emitted = run.cand_n;
+        ctx->topk_last_matched = run.matched;
+    }
+    return run;
+}
+
+static pb::PartialHit make_hit(const SplitView& sv, const SortPlan& sp,
+                               uint32_t doc, float score) {
+    pb::PartialHit h;
+    h.split_id = sv.split_id;
+    h.segment_ord = sv.segment_ord;
+    h.doc_id = doc;
+    if (!sp.specs.empty()) h.sort_value = sort_value_of(sp.specs[0], doc, score);
+    if (sp.specs.size() > 1) h.sort_value2 = sort_value_of(sp.specs[1], doc, score);
+    return h;
+}
+
+// PartialHits of the leaf's page, best first
+static void build_hits(std::vector<pb::PartialHit>& hits, const SplitView& sv,
+                       const SortPlan& sp, bool fq_scoring, TopkSelector& sel,
+                       uint64_t leaf_max_hits, bool trivial_hits) {
+    if (trivial_hits) {
+        // hits enumerable without the kernel: doc-id order (desc default)
+        uint64_t k = std::min<uint64_t>(leaf_max_hits, sv.num_docs);
+        for (uint64_t i = 0; i < k; ++i) {
+            uint32_t doc = sp.order1 == 1 ? uint32_t(sv.num_docs - 1 - i)
+                                          : uint32_t(i);
+            hits.push_back(make_hit(sv, sp, doc, 0.f));
+        }
+        return;
+    }
+    // build hits from the survivors; with search_after, the exact
+    // cursor filter runs before truncation and the selection widens
+    // (growing K) until the page is full or the band is exhausted
+    const std::vector<uint64_t>& top_keys = sel.top_keys;
+    do {
+        hits.clear();
+        hits.reserve(top_keys.size() / (sp.wide ? 2 : 1));
+        if (sp.wide) {
+            // survivors carry (selection key, score|doc); the exact
+            // reference order ((sort_value, sort_value2, GlobalDocId),
+            // sorting.md:14-26) is re-established over the survivors
+            size_t n = top_keys.size() / 2;
+            for (size_t i = 0; i < n; ++i) {
+                uint64_t aux = top_keys[2 * i + 1];
+                uint32_t doc = uint32_t(aux);
+                float score = 0.f;
+                if (fq_scoring) {
+                    uint32_t b = uint32_t(aux >> 32);
+                    memcpy(&score, &b, 4);
                 }
-            } else if (d.kind == AggDef::COMPOSITE) {
-                // decode packed 63-bit keys into the canonical per-source
-                // byte encoding (split-local ords -> term strings) so the
-                // cross-split QAGG merge compares composite tuples directly
-                r.kind = 3;
-                r.key_kind = 9;
-                if (a.n_buckets) {
-                    uint32_t slots = (a.n_buckets - 2) >> 1;
-                    if (counts[2 * uint64_t(slots) + 1])
-                        throw std::runtime_error(
-                            "composite hash table overflow");
-                    // recompute per-source widths exactly as plan_aggs did
-                    uint32_t width[4] = {0, 0, 0, 0};
-                    for (size_t si = 0; si < d.comp.size(); ++si) {
-                        const CompSource& cs = d.comp[si];
-                        const FastFieldView* sf = ap.comp_fields[i][si];
-                        uint64_t miss = cs.missing_bucket ? 1 : 0;
-                        uint64_t nv;
-                        if (cs.is_histo) {
-                            double mn, mx;
-                            col_min_max(*sf, &mn, &mx);
-                            int64_t b0 = int64_t(
-                                std::floor((mn - cs.offset) / cs.interval));
-                            int64_t b1 = int64_t(
-                                std::floor((mx - cs.offset) / cs.interval));
-                            nv = uint64_t(b1 - b0 + 1) + miss;
-                        } else {
-                            nv = uint64_t(sf->cardinality) + miss;
-                        }
-                        width[si] = comp_key_bits(nv);
-                    }
-                    auto decode_key = [&](uint64_t key) {
-                        std::string ck;
-                        for (size_t si = 0; si < d.comp.size(); ++si) {
-                            const CompSource& cs = d.comp[si];
-                            uint64_t comp = (key >> a.c_shift[si]) &
-                                            ((1ull << width[si]) - 1);
-                            uint64_t miss = cs.missing_bucket ? 1 : 0;
-                            if (miss && comp == 0) {
-                                comp_encode_null(ck);
-                            } else if (cs.is_histo) {
-                                double v = double(a.c_base[si] +
-                                                  int64_t(comp - miss)) *
-                                               cs.interval +
-                                           cs.offset;
-                                comp_encode_f64(ck, v);
-                            } else {
-                                comp_encode_str(
-                                    ck, ap.comp_fields[i][si]->dict_entry(
-                                            uint32_t(comp - miss)));
-                            }
-                        }
-                        return ck;
-                    };
-                    for (uint64_t s2 = 0; s2 < slots; ++s2) {
-                        uint64_t key = counts[2 * s2], c = counts[2 * s2 + 1];
-                        if (key != ~0ull && c)
-                            r.term_counts.emplace_back(decode_key(key), c);
-                    }
-                    std::sort(r.term_counts.begin(), r.term_counts.end());
+                hits.push_back(make_hit(sv, sp, doc, score));
+            }
+        } else {
+            const bool asc = sp.sort_asc();
+            for (uint64_t key : top_keys) {
+                uint32_t kh = uint32_t(key >> 32), kl = uint32_t(key);
+                if (asc) {
+                    kh = ~kh;
+                    kl = ~kl;
                 }
-            } else if (d.kind == AggDef::METRIC &&
-                       d.metric.kind == MetricAgg::PERCENTILES) {
-                r.kind = 6;
+                float score = 0.f;
+                if (fq_scoring) {
+                    uint32_t b = (kh & 0x80000000u) ? (kh & ~0x80000000u) : ~kh;
+                    memcpy(&score, &b, 4);
+                }
+                hits.push_back(make_hit(sv, sp, kl, score));
+            }
+        }
+        if (sp.after) {
+            const bool mixed1 = sp.mixed(0), mixed2 = sp.mixed(1);
+            hits.erase(std::remove_if(hits.begin(), hits.end(),
+                                      [&](const pb::PartialHit& h) {
+                                          return !after_cursor(
+                                              h, *sp.after, sp.ck1, sp.ck2,
+                                              sp.order1, sp.order2, mixed1,
+                                              mixed2);
+                                      }),
+                       hits.end());
+        }
+        size_t k = std::min<size_t>(leaf_max_hits, hits.size());
+        std::partial_sort(hits.begin(), hits.begin() + k, hits.end(),
+                          [&](const pb::PartialHit& a, const pb::PartialHit& b) {
+                              return hit_before(a, b, sp.order1, sp.order2);
+                          });
+        hits.resize(k);
+    } while (sel.grow(hits.size()));
+}
+
+// one STATS_SLOT_BYTES device stats slot (AggDev::n_sub, gpu_types.h)
+static StatsPayload read_stats_slot(const uint8_t* slot) {
+    StatsPayload sp;
+    uint64_t mn, mx;
+    memcpy(&sp.count, slot, 8);
+    memcpy(&sp.sum, slot + 8, 8);
+    memcpy(&mn, slot + 16, 8);
+    memcpy(&mx, slot + 24, 8);
+    memcpy(&sp.sum_sq, slot + 32, 8);
+    if (sp.count) {
+        sp.min = u64_to_f64(mn);
+        sp.max = u64_to_f64(mx);
+    }
+    return sp;
+}
+
+// the device output of aggregation i; agg_out is the host copy of the
+// results region that starts at r_agg
+struct AggOut {
+    const AggDef& d;
+    const AggDev& a;
+    const uint8_t* agg_out;
+    size_t r_agg;
+    const uint8_t* at(uint64_t results_off) const {
+        return agg_out + (results_off - r_agg);
+    }
+    const uint64_t* counts() const { return (const uint64_t*)at(a.counts_out); }
+};
+
+static void decode_terms(const AggOut& o, const FastFieldView* f,
+                         uint64_t matched, AggResult& r) {
+    const AggDef& d = o.d;
+    const AggDev& a = o.a;
+    const uint64_t* counts = o.counts();
+    if (!a.n_buckets) return;
+    if (a.nulls_off || a.offsets_off) {
+        uint64_t m = 0;
+        memcpy(&m, o.at(a.matched_out), 8);
+        r.terms_matched_docs = m;
+    } else {
+        // non-nullable column: every matched doc has a value
+        r.terms_matched_docs = matched;
+    }
+    if (a.kind == AGGD_TERMS_NUM) {
+        r.key_kind = f->type == FastFieldView::U64   ? 1
+                     : f->type == FastFieldView::F64 ? 3
+                                                     : 2;
+        uint32_t slots = (a.n_buckets - 2) >> 1;
+        if (counts[2 * uint64_t(slots) + 1])
+            throw std::runtime_error("numeric terms hash table overflow");
+        for (uint64_t s2 = 0; s2 < slots; ++s2) {
+            uint64_t key = counts[2 * s2], c = counts[2 * s2 + 1];
+            if (key != ~0ull && c)
+                r.term_counts.emplace_back(num_term_key(key), c);
+        }
+        if (uint64_t sc2 = counts[2 * uint64_t(slots)])
+            r.term_counts.emplace_back(num_term_key(~0ull), sc2);
+        std::sort(r.term_counts.begin(), r.term_counts.end());
+    } else {
+        const uint8_t* subs = o.at(a.sub_out);
+        for (uint32_t ord = 0; ord < a.n_buckets; ++ord) {
+            if (!counts[ord]) continue;
+            r.term_counts.emplace_back(f->dict_entry(ord), counts[ord]);
+            if (!a.n_sub) continue;
+            std::vector<StatsPayload> ts(d.sub.size());
+            for (uint32_t s = 0; s < a.n_sub; ++s)
+                ts[s] = read_stats_slot(
+                    subs + (uint64_t(ord) * a.n_sub + s) * STATS_SLOT_BYTES);
+            r.term_subs.push_back(std::move(ts));
+        }
+    }
+    if (d.kind == AggDef::TERMS)
+        truncate_terms_split(r, effective_split_size(d.size, d.split_size),
+                             d.order_target, d.order_asc, &d.sub);
+}
+
+// decode packed 63-bit keys into the canonical per-source byte encoding
+// (split-local ords -> term strings) so the cross-split QAGG merge compares
+// composite tuples directly
+static void decode_composite(
+    const AggOut& o, const std::array<const FastFieldView*, 4>& fields,
+    const std::array<uint32_t, 4>& width, AggResult& r) {
+    const AggDef& d = o.d;
+    const AggDev& a = o.a;
+    const uint64_t* counts = o.counts();
+    r.key_kind = 9;
+    if (!a.n_buckets) return;
+    uint32_t slots = (a.n_buckets - 2) >> 1;
+    if (counts[2 * uint64_t(slots) + 1])
+        throw std::runtime_error("composite hash table overflow");
+    for (uint64_t s2 = 0; s2 < slots; ++s2) {
+        uint64_t key = counts[2 * s2], c = counts[2 * s2 + 1];
+        if (key == ~0ull || !c) continue;
+        std::string ck;
+        for (size_t si = 0; si < d.comp.size(); ++si) {
+            const CompSource& cs = d.comp[si];
+            uint64_t comp = (key >> a.c_shift[si]) & ((1ull << width[si]) - 1);
+            uint64_t miss = cs.missing_bucket ? 1 : 0;
+            if (miss && comp == 0) {
+                comp_encode_null(ck);
+            } else if (cs.is_histo) {
+                double v = double(a.c_base[si] + int64_t(comp - miss)) *
+                               cs.interval +
+                           cs.offset;
+                comp_encode_f64(ck, v);
+            } else {
+                comp_encode_str(ck, fields[si]->dict_entry(uint32_t(comp - miss)));
+            }
+        }
+        r.term_counts.emplace_back(std::move(ck), c);
+    }
+    std::sort(r.term_counts.begin(), r.term_counts.end());
+}
+
+static void decode_histogram(const AggOut& o, AggResult& r) {
+    const AggDef& d = o.d;
+    const AggDev& a = o.a;
+    const uint64_t* counts = o.counts();
+    for (auto& sdef : d.sub)
+        r.sub_kinds.push_back(sdef.kind == MetricAgg::PERCENTILES ? 1 : 0);
+    const uint8_t* subs = o.at(a.sub_out);
+    const uint64_t* pwords =
+        a.p_si != 0xFF ? (const uint64_t*)o.at(a.p_out) : nullptr;
+    for (uint32_t bi = 0; bi < a.n_buckets; ++bi) {
+        if (!counts[bi]) continue;
+        AggBucket b;
+        b.key = double(a.base_index + int64_t(bi)) * d.interval + d.offset;
+        b.doc_count = counts[bi];
+        b.sub.resize(d.sub.size());
+        b.psub.resize(d.sub.size());
+        if (pwords) {
+            const uint64_t* pw = pwords + uint64_t(bi) * (a.p_n_keys + 1);
+            SketchPayload& pp = b.psub[a.p_si];
+            pp.zero = pw[0];
+            for (uint32_t j = 1; j <= a.p_n_keys; ++j)
+                if (pw[j]) pp.counts[a.p_k_lo + int32_t(j) - 1] = pw[j];
+        }
+        for (uint32_t s = 0; s < a.n_sub; ++s) {
+            if (s == a.p_si) continue;
+            b.sub[s] = read_stats_slot(
+                subs + (uint64_t(bi) * a.n_sub + s) * STATS_SLOT_BYTES);
+        }
+        r.buckets.push_back(std::move(b));
+    }
+}
+
+// aggregation assembly (QAGG1 intermediate) from the downloaded results
+static void decode_aggs(const AggPlan& ap, size_t r_agg, const uint8_t* agg_out,
+                        uint64_t matched, IntermediateAggResults& out) {
+    for (size_t i = 0; i < ap.defs.size(); ++i) {
+        const AggDef& d = ap.defs[i];
+        const AggDev& a = ap.devs[i];
+        const AggOut o{d, a, agg_out, r_agg};
+        AggResult r;
+        r.name = d.name;
+        r.kind = agg_result_kind(d);
+        for (auto& s : d.sub) r.sub_names.push_back(s.name);
+        switch (r.kind) {
+            case 3:
+                if (d.kind == AggDef::COMPOSITE)
+                    decode_composite(o, ap.comp_fields[i], ap.comp_width[i], r);
+                else decode_terms(o, ap.fields[i], matched, r);
+                break;
+            case 6:
                 if (a.n_buckets) {
+                    const uint64_t* counts = o.counts();
                     r.sketch.zero = counts[0];
                     for (uint32_t j = 1; j < a.n_buckets; ++j)
                         if (counts[j])
-                            r.sketch.counts[a.p_k_lo + int32_t(j) - 1] =
-                                counts[j];
+                            r.sketch.counts[a.p_k_lo + int32_t(j) - 1] = counts[j];
                 }
-            } else if (d.kind == AggDef::METRIC) {
-                r.kind = 5;
-                if (a.n_buckets) {
-                    const uint8_t* slot = agg_out_p + (a.counts_out - r_agg);
-                    StatsPayload sp2;
-                    uint64_t mn, mx;
-                    memcpy(&sp2.count, slot, 8);
-                    memcpy(&sp2.sum, slot + 8, 8);
-                    memcpy(&mn, slot + 16, 8);
-                    memcpy(&mx, slot + 24, 8);
-                    memcpy(&sp2.sum_sq, slot + 32, 8);
-                    if (sp2.count) {
-                        sp2.min = u64_to_f64(mn);
-                        sp2.max = u64_to_f64(mx);
-                    }
-                    r.metric = sp2;
-                }
-            } else if (d.kind == AggDef::RANGE) {
-                r.kind = 4;
+                break;
+            case 5:
+                if (a.n_buckets) r.metric = read_stats_slot(o.at(a.counts_out));
+                break;
+            case 4:
                 for (uint32_t ri = 0; ri < a.n_buckets; ++ri) {
-                    if (!counts[ri]) continue;
+                    if (!o.counts()[ri]) continue;
                     AggBucket b;
                     b.key = double(ri);  // range index; finalize maps back
-                    b.doc_count = counts[ri];
+                    b.doc_count = o.counts()[ri];
                     r.buckets.push_back(std::move(b));
                 }
-            } else {
-                r.kind = d.kind == AggDef::DATE_HISTOGRAM ? 1 : 2;
-                for (auto& sdef : d.sub)
-                    r.sub_kinds.push_back(
-                        sdef.kind == MetricAgg::PERCENTILES ? 1 : 0);
-                const uint8_t* subs = agg_out_p + (a.sub_out - r_agg);
-                const uint64_t* pwords =
-                    a.p_si != 0xFF
-                        ? (const uint64_t*)(agg_out_p + (a.p_out - r_agg))
-                        : nullptr;
-                for (uint32_t bi = 0; bi < a.n_buckets; ++bi) {
-                    if (!counts[bi]) continue;
-                    AggBucket b;
-                    b.key = double(a.base_index + int64_t(bi)) * d.interval + d.offset;
-                    b.doc_count = counts[bi];
-                    b.sub.resize(d.sub.size());
-                    b.psub.resize(d.sub.size());
-                    if (pwords) {
-                        const uint64_t* pw =
-                            pwords + uint64_t(bi) * (a.p_n_keys + 1);
-                        SketchPayload& pp = b.psub[a.p_si];
-                        pp.zero = pw[0];
-                        for (uint32_t j = 1; j <= a.p_n_keys; ++j)
-                            if (pw[j])
-                                pp.counts[a.p_k_lo + int32_t(j) - 1] = pw[j];
-                    }
-                    for (uint32_t s = 0; s < a.n_sub; ++s) {
-                        if (s == a.p_si) continue;
-                        const uint8_t* slot = subs + (uint64_t(bi) * a.n_sub + s) * 40;
-                        StatsPayload sp2;
-                        uint64_t mn, mx;
-                        memcpy(&sp2.count, slot, 8);
-                        memcpy(&sp2.sum, slot + 8, 8);
-                        memcpy(&mn, slot + 16, 8);
-                        memcpy(&mx, slot + 24, 8);
-                        memcpy(&sp2.sum_sq, slot + 32, 8);
-                        if (sp2.count) {
-                            sp2.min = u64_to_f64(mn);
-                            sp2.max = u64_to_f64(mx);
-                        }
-                        b.sub[s] = sp2;
-                    }
-                    r.buckets.push_back(std::move(b));
-                }
-            }
-            out.aggs.aggs.push_back(std::move(r));
+                break;
+            default:
+                decode_histogram(o, r);
         }
+        out.aggs.push_back(std::move(r));
+    }
+}
+
+static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
+                                    const pb::SearchRequest& req, const Schema& schema) {
+    SplitResult out;
+    StageTimer timer;
+    const SplitView& sv = ds.view;
+    ctx->hitsets.begin_query();  // unpin previous query's bitmap entries
+
+    PlanNode plan = leaf_plan(ctx, sv, req, schema);
+    SortPlan sp = make_sort_plan(sv, req);
+    FlatQuery fq = flatten_or_bitmap(ctx, ds, plan, schema, sp.scoring);
+    // report required terms flattening proved absent; the caller inserts
+    // into the absence cache (for multi-segment splits only terms absent
+    // from EVERY segment qualify)
+    out.absent_required = fq.absent_required;
+    const uint64_t leaf_max_hits = req.max_hits + req.start_offset;
+    const bool do_aggs = req.aggregation_request.has_value();
+
+    if (fq.match_none || sv.num_docs == 0) {
+        if (do_aggs) {
+            empty_agg_shapes(*req.aggregation_request, out.aggs);
+            out.has_aggs = true;
+        }
+        out.micros = timer.micros();
+        return out;
+    }
+
+    const uint32_t n_tiles = (sv.num_docs + TILE_DOCS - 1) / TILE_DOCS;
+    const bool pure_match_all =
+        fq.match_all && fq.preds.empty() && fq.terms.empty();
+    // hits trivially enumerable only under doc-id order (leaf.rs default)
+    const bool trivial_hits = pure_match_all && sp.specs.empty() && !sp.after;
+    // candidate collection: needed unless hits are trivially enumerable
+    const bool collect = leaf_max_hits > 0 && !trivial_hits && !fq.match_none;
+    const bool need_kernel = !pure_match_all || do_aggs || collect;
+
+    // ---- scratch assembly (descriptors + ktabs + block ranges), one H2D
+    TermTables tt = build_term_tables(sv, fq);
+    ScratchLayout L = layout_results_head(n_tiles);
+    AggPlan ap;
+    if (do_aggs)
+        ap = plan_aggs(sv, *req.aggregation_request, ctx->agg_bucket_limit,
+                       L.r_agg);
+    layout_finish(L, tt, fq, ap, collect ? sv.num_docs : 0, sp.wide);
+    eager_pred_flags(sv, fq);
+    timer.mark("plan");
+    // per-term block ranges come from the split-level device cache
+    // (term_ranges_addr): first query pays the walk+upload, repeats don't
+    ctx->h_scratch.ensure(L.scratch_bytes);
+    for (size_t i = 0; i < fq.terms.size(); ++i) {
+        const FlatQuery::FTerm& t = fq.terms[i];
+        tt.terms[i].ranges_addr =
+            term_ranges_addr(ctx, ds, t.f, t.tid, n_tiles, sv.num_docs);
+    }
+    timer.mark("ranges");
+    assemble_scratch(ctx->h_scratch.p, L, tt, fq, ap);
+    timer.mark("assembly");
+
+    uint64_t matched = sv.num_docs;  // pure match_all, no aggs: no kernel
+    TopkSelector sel(ctx, sp.wide, sp.after != nullptr, leaf_max_hits);
+    if (need_kernel) {
+        qw_ensure_acct(ctx, ctx->d_scratch, L.scratch_bytes);
+        qw_ensure_acct(ctx, ctx->d_results, L.results_bytes);
+        sel.attach(L);
+        enqueue_uploads(ctx, L, ap, do_aggs);
+        TileLaunch tl = fill_query_dev(ctx, ds, fq, sp, tt, ap, L, collect,
+                                       do_aggs, leaf_max_hits, n_tiles);
+        TileRun run = run_leaf_tile(ctx, sv, tl, L, ap, collect, do_aggs, sel, timer);
+        matched = run.matched;
+        if (collect && run.cand_n > 0) {
+            sel.band_n = run.cand_n;
+            if (sp.after) sel.compact_cursor_band(cursor_ceil_key(sp, fq.scoring));
+            if (sel.band_n > 0) {
+                sel.select(std::min<uint64_t>(
+                    leaf_max_hits + (sp.after ? 1024 : 0), sel.band_n));
+                timer.mark("topk_select");
+            }
+        }
+    }
+    if (pure_match_all) matched = sv.num_docs;
+    out.num_hits = matched;
+
+    if (leaf_max_hits > 0)
+        build_hits(out.hits, sv, sp, fq.scoring, sel, leaf_max_hits, trivial_hits);
+    timer.mark("build_hits");
+
+    if (do_aggs) {
+        // downloaded asynchronously with the counts batch (pinned)
+        ctx->h_agg.ensure(ap.out_bytes + 64);
+        decode_aggs(ap, L.r_agg, ctx->h_agg.p, matched, out.aggs);
         out.has_aggs = true;
     }
-    mark("aggs_assembly");
+    timer.mark("aggs_assembly");
 
-    out.micros = uint64_t(std::chrono::duration_cast<std::chrono::microseconds>(
-                              std::chrono::steady_clock::now() - t0)
-                              .count());
+    out.micros = timer.micros();
     return out;
 }
 
@@ -2677,9 +2813,8 @@ static SplitResult search_device_split(qw_ctx* ctx, const DeviceSplit& ds,
                 AbsenceCache::key(sid, kv.first.first, kv.first.second));
     uint64_t leaf_max = req.max_hits + req.start_offset;
     if (segs.size() > 1 && leaf_max > 0 && !out.hits.empty()) {
-        int order1 = req.sort_fields.empty() ? 1 : req.sort_fields[0].sort_order;
-        int order2 =
-            req.sort_fields.size() > 1 ? req.sort_fields[1].sort_order : 1;
+        int order1, order2;
+        request_sort_orders(req, &order1, &order2);
         size_t k = std::min<uint64_t>(leaf_max, out.hits.size());
         std::partial_sort(out.hits.begin(), out.hits.begin() + k,
                           out.hits.end(),

@@ -1326,6 +1326,101 @@ def test_terms_sub_aggregations():
             ej["by_svc"]["sum_other_doc_count"]
 
 
+# ------------------------------------------------- every decode path, small
+# One aggregation kind per case so a wrong shape names its kind. 777 docs:
+# one tile, not a multiple of 64, nullable sub and source columns.
+DECODE_SCHEMA = {"timestamp_field": None, "fields": [
+    {"name": "timestamp", "type": "datetime", "fast": True},
+    {"name": "severity_text", "type": "text", "tokenizer": "raw", "fast": True},
+    {"name": "body", "type": "text"},
+    {"name": "tenant_id", "type": "u64", "fast": True},
+    {"name": "svc", "type": "str", "fast": True},
+    {"name": "lat", "type": "f64", "fast": True},
+    {"name": "code", "type": "u64", "fast": True}]}
+DECODE_NDOCS = 777
+DECODE_CASES = {
+    "date_histogram_stats_percentiles": {"h": {
+        "date_histogram": {"field": "timestamp", "fixed_interval": "60000ms"},
+        "aggs": {"st": {"stats": {"field": "lat"}},
+                 "lp": {"percentiles": {"field": "lat", "keyed": False}}}}},
+    "histogram_stats": {"h": {
+        "histogram": {"field": "tenant_id", "interval": 2},
+        "aggs": {"st": {"extended_stats": {"field": "lat"}}}}},
+    "terms_stats": {"t": {
+        "terms": {"field": "svc", "size": 10},
+        "aggs": {"st": {"stats": {"field": "lat"}},
+                 "mx": {"max": {"field": "code"}}}}},
+    "terms_numeric": {"n": {"terms": {"field": "tenant_id", "size": 10}}},
+    "cardinality": {"c": {"cardinality": {"field": "svc"}}},
+    "range": {"r": {"range": {"field": "code", "ranges": [
+        {"to": 300.0}, {"from": 300.0, "to": 450.0}, {"from": 450.0}]}}},
+    "stats_metric": {"m": {"stats": {"field": "lat"}}},
+    "percentiles_metric": {"p": {"percentiles": {"field": "lat",
+                                                  "percents": [50, 95]}}},
+    "composite_histogram_missing": {"c": {"composite": {"size": 100, "sources": [
+        {"s": {"terms": {"field": "svc", "missing_bucket": True}}},
+        {"r": {"histogram": {"field": "code", "interval": 100,
+                             "missing_bucket": True}}}]}}},
+}
+DECODE_QUERIES = {
+    "all": {"type": "match_all"},
+    "some": {"type": "term", "field": "severity_text", "value": "ERROR"},
+    # matches nothing: the shaped empty response
+    "none": {"type": "term", "field": "severity_text", "value": "ABSENT"},
+}
+
+
+@pytest.fixture(scope="module")
+def decode_searchers():
+    import random
+    rng = random.Random(17)
+    docs = []
+    for i in range(DECODE_NDOCS):
+        d = {"timestamp": (1700000000 + i) * 1000,
+             "severity_text": "INFO" if i % 3 else "ERROR", "body": "x",
+             "tenant_id": i % 7}
+        if rng.random() < 0.8:
+            d["svc"] = rng.choice(["api", "ing", "jan"])
+        if rng.random() < 0.85:
+            d["lat"] = round(rng.uniform(0.5, 900.0), 3)
+        if rng.random() < 0.9:
+            d["code"] = rng.choice([200, 204, 404, 500])
+        docs.append(d)
+    w = splitgen.SplitWriter(DECODE_SCHEMA, "dec-0")
+    w.add_documents(docs)
+    data = w.finalize()
+    gpu, cpu = GpuSearcher(device=0), OracleSearcher()
+    gpu.add_split("dec-0", data)
+    cpu.add_split("dec-0", data)
+    return gpu, cpu
+
+
+@pytest.mark.parametrize("qname", sorted(DECODE_QUERIES))
+@pytest.mark.parametrize("case", sorted(DECODE_CASES))
+def test_agg_decode_paths_small_split(decode_searchers, case, qname):
+    """Each aggregation kind's host decode, and its shaped empty response,
+    against the oracle. Keys, counts, min/max and sketch buckets are exact.
+    Sums are f64 atomics on the device, so they may differ from the oracle's
+    serial sum by reordering: at most 777 addends of magnitude <= 900 bound
+    that by 777 * 2^-53 ~ 1e-13 relative, and the variance's cancellation
+    (mean^2 against sum_sq/n, a factor ~4 here) keeps it below 1e-12; the
+    file's approx_json (1e-9) is wider than needed and catches any wrong
+    slot."""
+    gpu, cpu = decode_searchers
+    aggs = DECODE_CASES[case]
+    req = make_leaf_request(DECODE_QUERIES[qname], DECODE_SCHEMA,
+                            [("dec-0", DECODE_NDOCS)], max_hits=0,
+                            aggregation=aggs)
+    g, e = gpu.leaf_search(req), cpu.leaf_search(req)
+    assert not g.get("failed_splits") and not e.get("failed_splits"), (g, e)
+    assert g.get("num_hits", 0) == e.get("num_hits", 0)
+    if qname == "none":
+        assert g.get("num_hits", 0) == 0
+    gj = gpu.finalize_agg_json(g["intermediate_aggregation_result"], aggs)
+    ej = cpu.finalize_agg_json(e["intermediate_aggregation_result"], aggs)
+    approx_json(gj, ej)
+
+
 def test_terms_order_key_on_gpu(searchers):
     # order=_key flows through the product's per-split truncation (assembly)
     gpu, cpu = searchers
