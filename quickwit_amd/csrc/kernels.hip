@@ -114,9 +114,18 @@ __device__ __forceinline__ uint64_t f64_sortable(double d) {
     return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
 }
 
+// presence bit of doc d in the null bitmap at split offset nulls_off
+// (u32, not bool: as a bool the test becomes a per-lane 64-bit mask that
+// stays live across the predicate loop)
+__device__ __forceinline__ uint32_t null_bit(const QueryDev& q, uint64_t nulls_off,
+                                             uint32_t d) {
+    const uint64_t* nulls = (const uint64_t*)(q.split + nulls_off);
+    return uint32_t(nulls[d >> 6] >> (d & 63)) & 1u;
+}
+
 // ------------------------------------------------------------- LDS layout
 // Byte offsets of the sections a given query shape uses; total is the
-// dynamic-LDS size the host passes at launch (keep tile_lds_bytes in sync).
+// dynamic-LDS size launch_leaf_tile starts from.
 template <bool NS, bool NB, bool NA, bool NC>
 struct SmemMap {
     static constexpr uint32_t score_off = 0;                       // f32[TILE_DOCS]
@@ -133,11 +142,6 @@ struct SmemMap {
     static constexpr uint32_t tail_off = agg_end;  // agg_matched[4] wave_base[4] cand_base
     static constexpr uint32_t total = tail_off + 4 * 4 + 4 * 4 + 4;
 };
-
-constexpr uint32_t tile_lds_bytes(bool ns, bool nb, bool na, bool nc) {
-    return (ns ? TILE_DOCS * 4 : 0) + (nb ? 2 * TILE_DOCS / 8 : 0) +
-           (nc ? 2 * TILE_DOCS / 8 : 0) + (na ? 2 * AGG_LDS_BUCKETS * 4 : 0) + 36;
-}
 
 // decode every block of `t` overlapping the tile; accumulate into score[] /
 // set bits in `bitset`. SCORE: add BM25 weight (or +1 count) into score.
@@ -335,10 +339,7 @@ __device__ void decode_term_tile(const QueryDev& q, const TermDev& t, uint32_t t
 __device__ __forceinline__ bool eval_pred(const QueryDev& q, const PredDev& p,
                                           uint32_t doc) {
     bool ok = true;
-    if (p.nulls_off) {
-        const uint64_t* nulls = (const uint64_t*)(q.split + p.nulls_off);
-        ok = (nulls[doc >> 6] >> (doc & 63)) & 1;
-    }
+    if (p.nulls_off) ok = null_bit(q, p.nulls_off, doc);
     if (p.type == PRED_BITSET) {
         const uint32_t* bm = (const uint32_t*)p.abs_bitmap;
         ok = (bm[doc >> 5] >> (doc & 31)) & 1;
@@ -431,10 +432,7 @@ __device__ __forceinline__ void terms_subs_add(const QueryDev& q, const AggDev& 
                                                uint64_t ord, uint32_t d) {
     for (uint32_t si = 0; si < a.n_sub; ++si) {
         if (!a.sub_width[si]) continue;  // missing sub column
-        if (a.sub_nulls_off[si]) {
-            const uint64_t* sn = (const uint64_t*)(q.split + a.sub_nulls_off[si]);
-            if (!((sn[d >> 6] >> (d & 63)) & 1)) continue;
-        }
+        if (a.sub_nulls_off[si] && !null_bit(q, a.sub_nulls_off[si], d)) continue;
         double sv = agg_value(q, a.sub_values_off[si], a.sub_width[si],
                               a.sub_is_i64[si], d);
         stats_slot_add(
@@ -475,10 +473,7 @@ __device__ __forceinline__ uint64_t agg_ord(const QueryDev& q, uint64_t values_o
 __device__ __forceinline__ uint64_t wide_sort_key(const QueryDev& q, uint32_t d,
                                                   float sc) {
     if (q.sort_src == 0) return 0;  // unknown sort field: None for every doc
-    if (q.sort_nulls_off) {
-        const uint64_t* nulls = (const uint64_t*)(q.split + q.sort_nulls_off);
-        if (!((nulls[d >> 6] >> (d & 63)) & 1)) return 0;
-    }
+    if (q.sort_nulls_off && !null_bit(q, q.sort_nulls_off, d)) return 0;
     uint64_t S = 0;
     if (q.sort_src == 1) {
         S = uint64_t(f32_sortable(sc)) << 32;
@@ -514,6 +509,58 @@ __device__ __forceinline__ int64_t histo_bucket(const QueryDev& q, const AggDev&
     }
     double v = agg_value(q, a.values_off, a.value_width, a.value_is_i64, doc);
     return int64_t(floor((v - a.offset) / a.interval)) - a.base_index;
+}
+
+// ------------------------------------------------- shared counting helpers
+// index of bucket i in an LDS count array held as `rep` (1 or 2) interleaved
+// copies; the end-of-kernel flush sums the pair, so every writer maps through here
+template <class I>
+__device__ __forceinline__ I lds_index(uint32_t rep, I i, uint32_t parity) {
+    return rep == 2 ? i * 2 + parity : i;
+}
+
+// count bucket i of agg `a`: in the LDS array when `a` owns LDS slot `slot`
+// (0 = histogram array, 1 = terms table), else in its global counts
+__device__ __forceinline__ void bucket_count_add(const QueryDev& q, const AggDev& a,
+                                                 uint32_t* lds_tab, uint32_t slot,
+                                                 uint64_t i) {
+    if (a.lds_slot == slot)
+        atomicAdd(&lds_tab[lds_index(a.lds_rep, i, lane_id() & 1u)], 1u);
+    else
+        atomicAdd((unsigned long long*)(q.results + a.counts_out) + i, 1ull);
+}
+
+// docs-with-value count of terms agg `ai`: the first four aggs have an LDS
+// counter (flushed at the end of the kernel), later ones count globally
+__device__ __forceinline__ void matched_add(const QueryDev& q, const AggDev& a,
+                                            uint32_t ai, uint32_t* lds_matched,
+                                            uint32_t n) {
+    if (ai < 4) atomicAdd(&lds_matched[ai], n);
+    else
+        atomicAdd((unsigned long long*)(q.results + a.matched_out),
+                  (unsigned long long)n);
+}
+
+// count `key` in a global open-addressing hash table (layout in
+// gpu_types.h): `slots` {key, count} pairs, then {count of the sentinel
+// value, overflow flag}. ~0 marks an empty slot, so key != ~0.
+__device__ __forceinline__ void hash_count_add(unsigned long long* tab,
+                                               uint32_t slots, uint64_t key) {
+    const unsigned long long SENT = ~0ull;
+    uint64_t h = key * 0x9E3779B97F4A7C15ull;
+    h ^= h >> 32;
+    uint32_t sl = uint32_t(h) & (slots - 1);
+    for (uint32_t pr = 0; pr < slots; ++pr) {
+        unsigned long long cur = tab[2 * sl];
+        if (cur == SENT)
+            cur = atomicCAS(&tab[2 * sl], SENT, (unsigned long long)key);
+        if (cur == SENT || cur == (unsigned long long)key) {
+            atomicAdd(&tab[2 * sl + 1], 1ull);
+            return;
+        }
+        sl = (sl + 1) & (slots - 1);
+    }
+    tab[2 * slots + 1] = 1ull;  // overflow
 }
 
 // ---------------------------------------------------------------- main kernel
@@ -767,10 +814,7 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
                 } else if (NA)
                     for (uint32_t ai = 0; ai < q.n_aggs; ++ai) {
                         const AggDev& a = aggs[ai];
-                        if (a.nulls_off) {
-                            const uint64_t* nulls = (const uint64_t*)(q.split + a.nulls_off);
-                            if (!((nulls[d >> 6] >> (d & 63)) & 1)) continue;
-                        }
+                        if (a.nulls_off && !null_bit(q, a.nulls_off, d)) continue;
                         if (a.kind == AGGD_TERMS) {
                             if (!a.n_buckets) continue;  // missing/non-str column
                             if (a.offsets_off) {
@@ -784,55 +828,20 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
                                     (const uint32_t*)(q.split + a.offsets_off);
                                 uint32_t s = offs[d], e2 = offs[d + 1];
                                 if (s == e2) continue;  // no value
-                                const uint8_t* col = q.split + a.values_off;
                                 for (uint32_t pos = s; pos < e2; ++pos) {
-                                    uint64_t o =
-                                        a.value_width == 1 ? col[pos]
-                                        : a.value_width == 2
-                                            ? ((const uint16_t*)col)[pos]
-                                            : ((const uint32_t*)col)[pos];
-                                    if (a.lds_slot == 1)
-                                        atomicAdd(
-                                            &sc_agg_terms[a.lds_rep == 2
-                                                              ? o * 2 +
-                                                                    (lane_id() & 1u)
-                                                              : o],
-                                            1u);
-                                    else
-                                        atomicAdd((unsigned long long*)(q.results +
-                                                                        a.counts_out) +
-                                                      o,
-                                                  1ull);
+                                    uint64_t o = agg_ord(q, a.values_off, a.value_width, pos);
+                                    bucket_count_add(q, a, sc_agg_terms, 1, o);
                                     if (a.n_sub) terms_subs_add(q, a, o, d);
                                 }
-                                if (ai < 4)
-                                    atomicAdd(&sc_agg_matched[ai], e2 - s);
-                                else
-                                    atomicAdd((unsigned long long*)(q.results +
-                                                                    a.matched_out),
-                                              (unsigned long long)(e2 - s));
+                                matched_add(q, a, ai, sc_agg_matched, e2 - s);
                                 continue;
                             }
                             uint64_t o = agg_ord(q, a.values_off, a.value_width, d);
-                            if (a.lds_slot == 1)
-                                atomicAdd(&sc_agg_terms[a.lds_rep == 2
-                                                            ? o * 2 + (lane_id() & 1u)
-                                                            : o],
-                                          1u);
-                            else
-                                atomicAdd((unsigned long long*)(q.results + a.counts_out) + o,
-                                          1ull);
+                            bucket_count_add(q, a, sc_agg_terms, 1, o);
                             if (a.n_sub) terms_subs_add(q, a, o, d);
                             // docs-with-value == matched docs for a
                             // non-nullable column: host uses num_hits instead
-                            if (a.nulls_off) {
-                                if (ai < 4)  // LDS count, flushed at the end
-                                    atomicAdd(&sc_agg_matched[ai], 1u);
-                                else
-                                    atomicAdd((unsigned long long*)(q.results +
-                                                                    a.matched_out),
-                                              1ull);
-                            }
+                            if (a.nulls_off) matched_add(q, a, ai, sc_agg_matched, 1u);
                         } else if (a.kind == AGGD_TERMS_NUM) {
                             // numeric-column terms: global open-addressing
                             // hash of the value's sortable bits (layout in
@@ -847,37 +856,9 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
                             unsigned long long* tab =
                                 (unsigned long long*)(q.results + a.counts_out);
                             uint32_t slots = (a.n_buckets - 2) >> 1;
-                            const unsigned long long SENT = ~0ull;
-                            if (v == SENT) {
-                                atomicAdd(&tab[2 * slots], 1ull);
-                            } else {
-                                uint64_t h = v * 0x9E3779B97F4A7C15ull;
-                                h ^= h >> 32;
-                                uint32_t sl = uint32_t(h) & (slots - 1);
-                                bool done = false;
-                                for (uint32_t pr = 0; pr < slots; ++pr) {
-                                    unsigned long long cur = tab[2 * sl];
-                                    if (cur == SENT)
-                                        cur = atomicCAS(&tab[2 * sl], SENT,
-                                                        (unsigned long long)v);
-                                    if (cur == SENT ||
-                                        cur == (unsigned long long)v) {
-                                        atomicAdd(&tab[2 * sl + 1], 1ull);
-                                        done = true;
-                                        break;
-                                    }
-                                    sl = (sl + 1) & (slots - 1);
-                                }
-                                if (!done) tab[2 * slots + 1] = 1ull;  // overflow
-                            }
-                            if (a.nulls_off) {
-                                if (ai < 4)
-                                    atomicAdd(&sc_agg_matched[ai], 1u);
-                                else
-                                    atomicAdd((unsigned long long*)(q.results +
-                                                                    a.matched_out),
-                                              1ull);
-                            }
+                            if (v == ~0ull) atomicAdd(&tab[2 * slots], 1ull);
+                            else hash_count_add(tab, slots, v);
+                            if (a.nulls_off) matched_add(q, a, ai, sc_agg_matched, 1u);
                         } else if (a.kind == AGGD_COMP) {
                             // composite: pack per-source components into a
                             // <=63-bit key (ordering == composite tuple asc),
@@ -888,12 +869,7 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
                             for (uint32_t si = 0; si < a.n_sub; ++si) {
                                 uint64_t comp = 0;
                                 bool present = true;
-                                if (a.sub_nulls_off[si]) {
-                                    const uint64_t* nu =
-                                        (const uint64_t*)(q.split +
-                                                          a.sub_nulls_off[si]);
-                                    present = (nu[d >> 6] >> (d & 63)) & 1;
-                                }
+                                if (a.sub_nulls_off[si]) present = null_bit(q, a.sub_nulls_off[si], d);
                                 uint64_t miss = (a.c_missing >> si) & 1;
                                 if (!present) {
                                     if (!miss) { okc = false; break; }
@@ -913,28 +889,8 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
                                 key |= comp << a.c_shift[si];
                             }
                             if (!okc) continue;
-                            unsigned long long* tab =
-                                (unsigned long long*)(q.results + a.counts_out);
-                            uint32_t slots = (a.n_buckets - 2) >> 1;
-                            const unsigned long long SENT = ~0ull;
-                            uint64_t h = key * 0x9E3779B97F4A7C15ull;
-                            h ^= h >> 32;
-                            uint32_t sl = uint32_t(h) & (slots - 1);
-                            bool done = false;
-                            for (uint32_t pr = 0; pr < slots; ++pr) {
-                                unsigned long long cur = tab[2 * sl];
-                                if (cur == SENT)
-                                    cur = atomicCAS(&tab[2 * sl], SENT,
-                                                    (unsigned long long)key);
-                                if (cur == SENT ||
-                                    cur == (unsigned long long)key) {
-                                    atomicAdd(&tab[2 * sl + 1], 1ull);
-                                    done = true;
-                                    break;
-                                }
-                                sl = (sl + 1) & (slots - 1);
-                            }
-                            if (!done) tab[2 * slots + 1] = 1ull;  // overflow
+                            hash_count_add((unsigned long long*)(q.results + a.counts_out),
+                                           (a.n_buckets - 2) >> 1, key);
                         } else if (a.kind == AGGD_PERC) {
                             if (!a.n_buckets) continue;
                             double v = agg_value(q, a.values_off, a.value_width,
@@ -948,14 +904,7 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
                             if (!a.values_off) continue;
                             double v = agg_value(q, a.values_off, a.value_width,
                                                  a.value_is_i64, d);
-                            uint8_t* slot = q.results + a.counts_out;
-                            atomicAdd((unsigned long long*)slot, 1ull);
-                            atomicAdd((double*)(slot + 8), v);
-                            atomicMin((unsigned long long*)(slot + 16),
-                                      (unsigned long long)f64_sortable(v));
-                            atomicMax((unsigned long long*)(slot + 24),
-                                      (unsigned long long)f64_sortable(v));
-                            atomicAdd((double*)(slot + 32), v * v);
+                            stats_slot_add(q.results + a.counts_out, v);
                         } else if (a.kind == AGGD_RANGE) {
                             if (!a.n_ranges) continue;
                             double v = agg_value(q, a.values_off, a.value_width,
@@ -973,22 +922,10 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
                         } else {
                             int64_t idx = histo_bucket(q, a, d);
                             if (idx < 0 || idx >= int64_t(a.n_buckets)) continue;
-                            if (a.lds_slot == 0)
-                                atomicAdd(&sc_agg_hist[a.lds_rep == 2
-                                                           ? uint32_t(idx) * 2 +
-                                                                 (lane_id() & 1u)
-                                                           : uint32_t(idx)],
-                                          1u);
-                            else
-                                atomicAdd((unsigned long long*)(q.results + a.counts_out) +
-                                              idx, 1ull);
+                            bucket_count_add(q, a, sc_agg_hist, 0, uint64_t(idx));
                             for (uint32_t si = 0; si < a.n_sub; ++si) {
                                 if (!a.sub_width[si]) continue;  // missing col
-                                if (a.sub_nulls_off[si]) {
-                                    const uint64_t* sn =
-                                        (const uint64_t*)(q.split + a.sub_nulls_off[si]);
-                                    if (!((sn[d >> 6] >> (d & 63)) & 1)) continue;
-                                }
+                                if (a.sub_nulls_off[si] && !null_bit(q, a.sub_nulls_off[si], d)) continue;
                                 double sv = agg_value(q, a.sub_values_off[si],
                                                       a.sub_width[si], a.sub_is_i64[si], d);
                                 if (si == a.p_si) {
@@ -1004,15 +941,9 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
                                               1ull);
                                     continue;
                                 }
-                                uint8_t* slot = q.results + a.sub_out +
-                                                (uint64_t(idx) * a.n_sub + si) * STATS_SLOT_BYTES;
-                                atomicAdd((unsigned long long*)slot, 1ull);
-                                atomicAdd((double*)(slot + 8), sv);
-                                atomicMin((unsigned long long*)(slot + 16),
-                                          (unsigned long long)f64_sortable(sv));
-                                atomicMax((unsigned long long*)(slot + 24),
-                                          (unsigned long long)f64_sortable(sv));
-                                atomicAdd((double*)(slot + 32), sv * sv);
+                                stats_slot_add(q.results + a.sub_out +
+                                                   (uint64_t(idx) * a.n_sub + si) * STATS_SLOT_BYTES,
+                                               sv);
                             }
                         }
                     }
@@ -1251,11 +1182,11 @@ inline uint32_t launch_leaf_tile(bool ns, bool nb, bool na, bool nc, dim3 grid,
                                  hipStream_t stream, const QueryDev& q,
                                  uint32_t tile_base, uint32_t tile_end,
                                  uint32_t do_count) {
-    uint32_t lds = tile_lds_bytes(ns, nb, na, nc);
     // runtime-optional staging sections (norms tile + K tables): pay LDS
     // only for what this query stages
-    if (ns && q.norms_stage_off) lds += TILE_DOCS;
-    if (ns && q.scoring && q.n_ktabs) lds += 1024 * q.n_ktabs;
+    uint32_t stage = 0;
+    if (ns && q.norms_stage_off) stage += TILE_DOCS;
+    if (ns && q.scoring && q.n_ktabs) stage += 1024 * q.n_ktabs;
     // top-K pruning has instantiations of its own (collecting shapes only),
     // so every unpruned launch runs the code it ran before pruning existed
     const bool pr = q.prune_k != 0;
@@ -1263,6 +1194,7 @@ inline uint32_t launch_leaf_tile(bool ns, bool nb, bool na, bool nc, dim3 grid,
         throw std::runtime_error("prune_k needs narrow candidate collection");
     #define QW_CASE(NS_, NB_, NA_, NC_)                                           \
         if (ns == NS_ && nb == NB_ && na == NA_ && nc == NC_) {                   \
+            const uint32_t lds = SmemMap<NS_, NB_, NA_, NC_>::total + stage;      \
             if (NC_ && pr)                                                        \
                 hipLaunchKernelGGL((k_leaf_tile_t<NS_, NB_, NA_, NC_, NC_>),      \
                                    grid, dim3(TILE_THREADS), lds, stream, q,      \

@@ -1361,6 +1361,27 @@ DECODE_CASES = {
         {"s": {"terms": {"field": "svc", "missing_bucket": True}}},
         {"r": {"histogram": {"field": "code", "interval": 100,
                              "missing_bucket": True}}}]}}},
+    # a5 (str terms) and a6 (numeric terms) are over nullable columns at
+    # aggregation index >= 4: their docs-with-value count goes to the global
+    # matched word, not one of the four LDS counters, and size 1 makes
+    # sum_other_doc_count depend on it
+    "six_aggs_late_nullable_terms": {
+        "a1": {"stats": {"field": "lat"}},
+        "a2": {"range": {"field": "code", "ranges": [{"to": 300.0}]}},
+        "a3": {"histogram": {"field": "tenant_id", "interval": 2}},
+        "a4": {"terms": {"field": "severity_text", "size": 1}},
+        "a5": {"terms": {"field": "svc", "size": 1}},
+        "a6": {"terms": {"field": "code", "size": 1}}},
+    # 1,553 buckets fit the LDS histogram array only unreplicated
+    "date_histogram_1553_buckets": {"h": {
+        "date_histogram": {"field": "timestamp", "fixed_interval": "500ms"}}},
+    # 3,105 buckets exceed the LDS array: global atomics
+    "date_histogram_3105_buckets": {"h": {
+        "date_histogram": {"field": "timestamp", "fixed_interval": "250ms"}}},
+    # the second histogram finds the LDS array taken: global atomics
+    "two_histograms": {
+        "h1": {"histogram": {"field": "tenant_id", "interval": 2}},
+        "h2": {"histogram": {"field": "code", "interval": 100}}},
 }
 DECODE_QUERIES = {
     "all": {"type": "match_all"},
