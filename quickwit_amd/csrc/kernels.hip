@@ -1492,4 +1492,224 @@ extern "C" __global__ void k_phrase_bitmap(const uint8_t* split, PhraseDev p,
     }
 }
 
+// ------------------------------------------------- sloppy phrase / prefix
+// k_phrase_window_bitmap: phrases with slop > 0 and multi-token phrase
+// prefixes. One WAVE per (posting of token 0, last-token
+// alternative): grid.x strides over token 0's postings, grid.y over the
+// alternatives (one for a sloppy phrase, the prefix expansions otherwise).
+//
+// With q_i = p_i - i, a document matches slop S iff some choice of one
+// position per token has sum_i |q_i - q_{i-1}| <= S. A total cost <= S never
+// leaves q_0 + [-S, S], so lane l in [0, 2S] stands for the offset d = l - S
+// and carries the cheapest cost of a choice of tokens 0..i that ends at
+// q_0 + d. One token more is a min-plus step with |.|, done as two log-step
+// shuffle scans. Lanes past 2S carry an infinite cost through the same
+// shuffles. S <= 31 keeps the window inside one wave.
+//
+// Every loop is bounded by a count read from the split (n_blocks, count, tf)
+// or by the launch (n_toks, n_alts); no wave waits on another.
+constexpr uint32_t PHRASE_MAX_SLOP = 31;
+constexpr uint32_t PHRASE_COST_INF = 1u << 20;
+
+// One 128-posting block decoded by the wave: lane l holds postings l and
+// l + 64. doc* are doc ids, tf* term frequencies (0 past count), pre* the
+// tf sums of the block's earlier postings (the position-stream offset).
+struct PhraseBlockLanes {
+    uint32_t doc0, doc1, tf0, tf1, pre0, pre1;
+};
+
+__device__ static PhraseBlockLanes phrase_decode_block(const uint32_t* payload,
+                                                       const SkipEntryDev& e,
+                                                       uint32_t lane) {
+    const uint32_t* gw = payload + e.word_off;
+    const uint32_t j0 = lane, j1 = lane + 64u;
+    // posting 0 is the block's first_doc; its stored gap is not a gap
+    uint32_t g0 = (j0 >= 1u && j0 < e.count) ? phrase_gap(gw, j0, e.id_bits) : 0u;
+    uint32_t g1 = j1 < e.count ? phrase_gap(gw, j1, e.id_bits) : 0u;
+    uint32_t s0 = wave_incl_scan_u32(g0);
+    uint32_t s1 = wave_incl_scan_u32(g1) + __shfl(s0, 63, 64);
+    PhraseBlockLanes b;
+    b.doc0 = e.first_doc + s0;
+    b.doc1 = e.first_doc + s1;
+    b.tf0 = j0 < e.count ? 1u : 0u;
+    b.tf1 = j1 < e.count ? 1u : 0u;
+    if (e.tf_bits) {
+        // tf fields start after the gap words (2*id_bits u64 = this many u32s)
+        const uint32_t* tfw = gw + ((128u * e.id_bits + 63u) / 64u) * 2;
+        if (j0 < e.count) b.tf0 = phrase_gap(tfw, j0, e.tf_bits) + 1u;
+        if (j1 < e.count) b.tf1 = phrase_gap(tfw, j1, e.tf_bits) + 1u;
+    }
+    uint32_t t0 = wave_incl_scan_u32(b.tf0);
+    uint32_t t1 = wave_incl_scan_u32(b.tf1) + __shfl(t0, 63, 64);
+    b.pre0 = t0 - b.tf0;
+    b.pre1 = t1 - b.tf1;
+    return b;
+}
+
+// posting j (wave-uniform) of a decoded block, broadcast to every lane
+__device__ __forceinline__ void phrase_block_pick(const PhraseBlockLanes& b,
+                                                  uint32_t j, uint32_t* doc,
+                                                  uint32_t* tf, uint32_t* pre) {
+    const int src = int(j & 63u);
+    uint32_t d0 = __shfl(b.doc0, src, 64), d1 = __shfl(b.doc1, src, 64);
+    uint32_t f0 = __shfl(b.tf0, src, 64), f1 = __shfl(b.tf1, src, 64);
+    uint32_t p0 = __shfl(b.pre0, src, 64), p1 = __shfl(b.pre1, src, 64);
+    *doc = j < 64u ? d0 : d1;
+    *tf = j < 64u ? f0 : f1;
+    *pre = j < 64u ? p0 : p1;
+}
+
+// find `doc` (wave-uniform) in a token's postings: skip-entry binary search,
+// then a ballot over the lane-decoded block. Outputs are wave-uniform.
+__device__ static bool phrase_find_doc(const uint8_t* split,
+                                       const PhraseTokDev& tk, uint32_t doc,
+                                       uint32_t lane, uint32_t* pos_off,
+                                       uint32_t* tf) {
+    const SkipEntryDev* skip = (const SkipEntryDev*)(split + tk.skip_off);
+    uint32_t lo = 0, hi = tk.n_blocks;  // first block with last_doc >= doc
+    while (lo < hi) {
+        uint32_t mid = (lo + hi) >> 1;
+        if (skip[mid].last_doc < doc) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo == tk.n_blocks) return false;
+    SkipEntryDev e = skip[lo];
+    if (e.first_doc > doc) return false;
+    PhraseBlockLanes b =
+        phrase_decode_block((const uint32_t*)(split + tk.payload_off), e, lane);
+    uint64_t m0 = __ballot(lane < e.count && b.doc0 == doc);
+    uint64_t m1 = __ballot(lane + 64u < e.count && b.doc1 == doc);
+    if (!(m0 | m1)) return false;
+    uint32_t j = m0 ? uint32_t(__ffsll((long long)m0)) - 1u
+                    : 64u + uint32_t(__ffsll((long long)m1)) - 1u;
+    uint32_t d, pre;
+    phrase_block_pick(b, j, &d, tf, &pre);
+    *pos_off = ((const uint32_t*)(split + tk.pos_start_off))[lo] + pre;
+    return true;
+}
+
+// is `want` one of the n ascending positions at P?
+__device__ __forceinline__ bool phrase_has_pos(const uint32_t* P, uint32_t n,
+                                               uint32_t want) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        uint32_t mid = (lo + hi) >> 1;
+        uint32_t v = P[mid];
+        if (v == want) return true;
+        if (v < want) lo = mid + 1;
+        else hi = mid;
+    }
+    return false;
+}
+
+// f[l] = min over l' of f[l'] + |l - l'| across the wave
+__device__ __forceinline__ uint32_t phrase_minplus_abs(uint32_t f, uint32_t lane) {
+    #pragma unroll
+    for (uint32_t k = 1; k < 64; k <<= 1) {
+        uint32_t u = __shfl_up(f, k, 64) + k;
+        if (lane >= k && u < f) f = u;
+    }
+    #pragma unroll
+    for (uint32_t k = 1; k < 64; k <<= 1) {
+        uint32_t u = __shfl_down(f, k, 64) + k;
+        if (lane + k < 64u && u < f) f = u;
+    }
+    return f;
+}
+
+// p.tok[0 .. n_toks-2] are the phrase's leading tokens, alts[a] stands in
+// for the last one. slop <= PHRASE_MAX_SLOP (host-checked; clamped here).
+extern "C" __global__ void __launch_bounds__(256)
+k_phrase_window_bitmap(const uint8_t* split, PhraseDev p,
+                       const PhraseTokDev* alts, uint32_t n_alts,
+                       uint32_t slop_in, uint32_t* bitmap) {
+    const uint32_t lane = lane_id();
+    const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint32_t n_waves = gridDim.x * (blockDim.x >> 6);
+    const uint32_t n = p.n_toks < PHRASE_MAX_TOKS ? p.n_toks : PHRASE_MAX_TOKS;
+    const uint32_t S = slop_in < PHRASE_MAX_SLOP ? slop_in : PHRASE_MAX_SLOP;
+    if (n < 2) return;
+    const PhraseTokDev& t0 = p.tok[0];
+    const SkipEntryDev* skip0 = (const SkipEntryDev*)(split + t0.skip_off);
+    const uint32_t* pay0 = (const uint32_t*)(split + t0.payload_off);
+    const uint32_t* ps0 = (const uint32_t*)(split + t0.pos_start_off);
+    const uint32_t n_post = t0.n_blocks * 128u;  // slots; short blocks skip
+
+    for (uint32_t a = blockIdx.y; a < n_alts; a += gridDim.y) {
+        const PhraseTokDev last = alts[a];
+        for (uint32_t t = wave; t < n_post; t += n_waves) {
+            const uint32_t blk = t >> 7, j = t & 127u;
+            SkipEntryDev e0 = skip0[blk];
+            if (j >= e0.count) continue;
+            PhraseBlockLanes b0 = phrase_decode_block(pay0, e0, lane);
+            uint32_t doc, tf0, pre0;
+            phrase_block_pick(b0, j, &doc, &tf0, &pre0);
+            if (doc >= p.num_docs) continue;
+            const uint32_t off0 = ps0[blk] + pre0;
+
+            // lane i keeps token i's (position offset, tf) in this doc
+            uint32_t my_off = 0, my_tf = 0;
+            bool ok = true;
+            for (uint32_t i = 1; i < n && ok; ++i) {
+                const PhraseTokDev& ti = i + 1 == n ? last : p.tok[i];
+                uint32_t off, tf;
+                ok = phrase_find_doc(split, ti, doc, lane, &off, &tf);
+                if (ok && lane == i) {
+                    my_off = off;
+                    my_tf = tf;
+                }
+            }
+            if (!ok) continue;
+
+            const uint32_t* P0 = (const uint32_t*)(split + t0.positions_off);
+            bool hit = false;
+            if (S == 0) {
+                // no window: lanes split the anchors, each tests the chain
+                bool mine = false;
+                for (uint32_t base = 0; base < tf0; base += 64u) {
+                    const uint32_t an = base + lane;
+                    const uint32_t pos0 = an < tf0 ? P0[off0 + an] : 0u;
+                    bool chain = an < tf0;
+                    for (uint32_t i = 1; i < n; ++i) {
+                        const PhraseTokDev& ti = i + 1 == n ? last : p.tok[i];
+                        const uint32_t* Pi =
+                            (const uint32_t*)(split + ti.positions_off);
+                        uint32_t oi = __shfl(my_off, int(i), 64);
+                        uint32_t ni = __shfl(my_tf, int(i), 64);
+                        uint64_t want = uint64_t(pos0) + i;
+                        chain = chain && want <= 0xFFFFFFFFull &&
+                                phrase_has_pos(Pi + oi, ni, uint32_t(want));
+                    }
+                    mine |= chain;
+                }
+                hit = __ballot(mine) != 0;
+            } else {
+                const bool active = lane <= 2u * S;
+                const int64_t d = int64_t(lane) - int64_t(S);
+                for (uint32_t an = 0; an < tf0 && !hit; ++an) {
+                    const uint32_t pos0 = P0[off0 + an];
+                    uint32_t cost = (active && d == 0) ? 0u : PHRASE_COST_INF;
+                    for (uint32_t i = 1; i < n; ++i) {
+                        const PhraseTokDev& ti = i + 1 == n ? last : p.tok[i];
+                        const uint32_t* Pi =
+                            (const uint32_t*)(split + ti.positions_off);
+                        uint32_t oi = __shfl(my_off, int(i), 64);
+                        uint32_t ni = __shfl(my_tf, int(i), 64);
+                        // p_i = q_0 + d + i; negative positions never match
+                        int64_t want = int64_t(pos0) + d + int64_t(i);
+                        bool present = active && want >= 0 &&
+                                       want <= 0xFFFFFFFFll &&
+                                       phrase_has_pos(Pi + oi, ni, uint32_t(want));
+                        uint32_t f = phrase_minplus_abs(cost, lane);
+                        cost = present && f < PHRASE_COST_INF ? f : PHRASE_COST_INF;
+                    }
+                    hit = __ballot(cost <= S) != 0;
+                }
+            }
+            if (hit && lane == 0)
+                atomicOr(&bitmap[doc >> 5], 1u << (doc & 31u));
+        }
+    }
+}
+
 }  // namespace qw

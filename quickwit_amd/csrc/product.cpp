@@ -33,6 +33,11 @@
 #include <string>
 #include <vector>
 
+// the plan layer accepts sloppy phrases and multi-token phrase prefixes only
+// here: the CPU oracle shares qast.h and has no evaluator for them, so it
+// keeps refusing them (defined before the first include that pulls qast.h in)
+#define QW_PHRASE_WINDOW 1
+
 #include "../../include/quickwit_amd.h"
 #include "fieldnorm.h"
 #include "minijson.h"
@@ -1333,6 +1338,8 @@ static pb::SortByValue sort_value_of(const SortSpec& s, uint32_t doc, float scor
 static uint8_t* resolve_hitset(qw_ctx* ctx, const DeviceSplit& ds,
                                const PlanNode& inner, const Schema& schema);
 
+static void record_kernel_time(qw_ctx* ctx, const char* name, float ms);
+
 // combine helper: dst op= src (op per k_bitmap_combine)
 static void bitmap_combine(qw_ctx* ctx, uint8_t* dst, const uint8_t* src,
                            size_t bm_bytes, uint32_t op) {
@@ -1461,17 +1468,17 @@ static uint8_t* resolve_hitset(qw_ctx* ctx, const DeviceSplit& ds,
             (void)hipFree(bm);
             throw std::runtime_error("phrase longer than 8 tokens (r2 limit)");
         }
-        PhraseDev p{};
-        p.n_toks = uint32_t(inner.phrase_toks.size());
-        p.num_docs = sv.num_docs;
-        for (size_t i = 0; i < inner.phrase_toks.size() && !none; ++i) {
-            const std::string& tok = inner.phrase_toks[i];
-            int64_t tid = f->find_term(tok.data(), tok.size());
-            if (tid < 0) {
-                none = true;  // absent token: phrase matches nothing
-                break;
-            }
-            PhraseTokDev& td = p.tok[i];
+        // slop > 0 or a prefix last token: k_phrase_window_bitmap, one wave
+        // per (driver posting, last-token alternative); DESIGN.md §7
+        const bool window = inner.prefix_last || inner.slop > 0;
+        const uint32_t slop = inner.prefix_last ? 0u : inner.slop;
+        if (slop > PHRASE_MAX_SLOP) {
+            (void)hipFree(bm);
+            throw std::runtime_error(
+                "phrase slop > 31 not supported (one wave holds the window)");
+        }
+        auto tok_dev = [&](int64_t tid) {
+            PhraseTokDev td{};
             td.skip_off = f->skip.off + f->h_skip_off[tid];
             td.payload_off = f->payload.off;
             td.pos_start_off =
@@ -1479,16 +1486,97 @@ static uint8_t* resolve_hitset(qw_ctx* ctx, const DeviceSplit& ds,
             td.positions_off = f->positions.off;
             td.n_blocks = f->h_n_blocks[tid];
             td.df = f->h_doc_freq[tid];
+            return td;
+        };
+        PhraseDev p{};
+        p.n_toks = uint32_t(inner.phrase_toks.size());
+        p.num_docs = sv.num_docs;
+        // the last token of a phrase prefix is no term: it is expanded below
+        size_t n_exact = inner.phrase_toks.size() - (inner.prefix_last ? 1 : 0);
+        for (size_t i = 0; i < n_exact && !none; ++i) {
+            const std::string& tok = inner.phrase_toks[i];
+            int64_t tid = f->find_term(tok.data(), tok.size());
+            if (tid < 0) {
+                none = true;  // absent token: phrase matches nothing
+                break;
+            }
+            p.tok[i] = tok_dev(tid);
+        }
+        // last-token alternatives: the token itself, or the first
+        // max_expansions dictionary terms (byte order) starting with it
+        std::vector<PhraseTokDev> alts;
+        if (window && !none) {
+            if (inner.prefix_last) {
+                const std::string& pre = inner.phrase_toks.back();
+                auto term_at = [&](uint32_t t, size_t* len) {
+                    *len = f->h_term_offsets[t + 1] - f->h_term_offsets[t];
+                    return (const char*)f->h_term_bytes + f->h_term_offsets[t];
+                };
+                uint32_t lo = 0, hi = f->num_terms;  // first term >= prefix
+                while (lo < hi) {
+                    uint32_t mid = (lo + hi) / 2;
+                    size_t sl;
+                    const char* s = term_at(mid, &sl);
+                    int c = memcmp(s, pre.data(), std::min(sl, pre.size()));
+                    if (c < 0 || (c == 0 && sl < pre.size())) lo = mid + 1;
+                    else hi = mid;
+                }
+                for (uint32_t t = lo;
+                     t < f->num_terms && alts.size() < inner.max_expansions;
+                     ++t) {
+                    size_t sl;
+                    const char* s = term_at(t, &sl);
+                    if (sl < pre.size() || memcmp(s, pre.data(), pre.size()))
+                        break;  // past the prefix's contiguous range
+                    alts.push_back(tok_dev(t));
+                }
+            } else {
+                alts.push_back(p.tok[p.n_toks - 1]);
+            }
+            if (alts.empty()) none = true;  // prefix without expansion
         }
         HIP_CHECK(hipMemsetAsync(bm, 0, bm_bytes, ctx->stream));
-        if (!none && p.tok[0].df) {
+        const char* kname = nullptr;
+        if (!window && !none && p.tok[0].df) {
             uint32_t grid =
                 std::min<uint32_t>(2048, (p.tok[0].df + 255) / 256);
+            kname = "k_phrase_bitmap";
+            HIP_CHECK(hipEventRecord(ctx->ev_start, ctx->stream));
             hipLaunchKernelGGL(k_phrase_bitmap, dim3(grid), dim3(256), 0,
                                ctx->stream, ds.d_image, p, (uint32_t*)bm);
+            HIP_CHECK(hipEventRecord(ctx->ev_stop, ctx->stream));
+        }
+        if (window && !none && p.tok[0].df) {
+            size_t alt_bytes = alts.size() * sizeof(PhraseTokDev);
+            try {
+                qw_ensure_acct(ctx, ctx->d_scratch, alt_bytes);
+            } catch (...) {
+                (void)hipFree(bm);
+                throw;
+            }
+            HIP_CHECK(hipMemcpyAsync(ctx->d_scratch.p, alts.data(), alt_bytes,
+                                     hipMemcpyHostToDevice, ctx->stream));
+            // 256 CUs x 32 waves = 2048 resident 4-wave blocks: grid.y takes
+            // up to 16 alternatives, grid.x what is left of the 2048; the
+            // kernel strides over the rest of both
+            uint32_t gy = uint32_t(std::min<size_t>(alts.size(), 16));
+            uint32_t slots = p.tok[0].n_blocks * 128u;  // one wave each
+            uint32_t gx = std::min<uint32_t>(2048u / gy, (slots + 3) / 4);
+            kname = "k_phrase_window_bitmap";
+            HIP_CHECK(hipEventRecord(ctx->ev_start, ctx->stream));
+            hipLaunchKernelGGL(k_phrase_window_bitmap, dim3(gx, gy), dim3(256),
+                               0, ctx->stream, ds.d_image, p,
+                               (const PhraseTokDev*)ctx->d_scratch.p,
+                               uint32_t(alts.size()), slop, (uint32_t*)bm);
+            HIP_CHECK(hipEventRecord(ctx->ev_stop, ctx->stream));
         }
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         HIP_CHECK(hipGetLastError());
+        if (kname) {
+            float ms = 0;
+            HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+            record_kernel_time(ctx, kname, ms);
+        }
         ctx->hitsets.put(key, bm, bm_bytes);
         return bm;
     }
@@ -1606,9 +1694,10 @@ static void collect_required_terms(
             break;
         case PlanNode::PHRASE:
             // every phrase token is required (the phrase cannot match if
-            // any token is absent)
-            for (const std::string& t : n.phrase_toks)
-                out.emplace_back(n.field, t);
+            // any token is absent), except a prefix last token: no term
+            for (size_t i = 0; i + (n.prefix_last ? 1 : 0) < n.phrase_toks.size();
+                 ++i)
+                out.emplace_back(n.field, n.phrase_toks[i]);
             break;
         case PlanNode::BOOL:
             for (const PlanNode& c : n.must) collect_required_terms(c, out);

@@ -212,6 +212,15 @@ struct PlanNode {
     // mode; needs record: position). Matching is unscored (const-score
     // semantics like term_set/wildcard).
     std::vector<std::string> phrase_toks;
+    // slop: a document matches iff one position p_i per token exists with
+    // sum_i |(p_i - i) - (p_{i-1} - (i-1))| <= slop (0 = consecutive).
+    // prefix_last: the last token is a prefix, standing for the first
+    // max_expansions dictionary terms that start with it (phrase_prefix;
+    // slop is ignored there). Both are accepted by the product build only
+    // (QW_PHRASE_WINDOW); see DESIGN.md §7.
+    uint32_t slop = 0;
+    bool prefix_last = false;
+    uint32_t max_expansions = 50;
 };
 
 // stable fingerprint of a plan subtree — the (split, subquery) key of the
@@ -232,6 +241,11 @@ inline void plan_fingerprint(const PlanNode& n, std::string& out) {
              int(n.lo.kind), (long long)n.lo.ival, int(n.hi.kind),
              (long long)n.hi.ival, (long long)n.minimum_should_match,
              double(n.boost), int(n.ci));
+    out += buf;
+    // a sloppy phrase, a phrase prefix and the plain phrase of the same
+    // tokens are three different doc sets
+    snprintf(buf, sizeof buf, "~%u:%d:%u|", n.slop, int(n.prefix_last),
+             n.max_expansions);
     out += buf;
     // str bounds live in sval and f64 bounds in fval (ival only truncates
     // them): two ranges differing there must not share a cached bitmap
@@ -487,7 +501,8 @@ inline PlanNode full_text_plan(const std::string& field, const std::string& text
 // full_text_query.rs phrase mode). Single-token phrases degrade to TERM;
 // zero tokens follow zero_terms_query like full_text_plan.
 inline PlanNode phrase_plan(const std::string& field, const std::string& text,
-                            const Schema& schema, bool zero_terms_all = false) {
+                            const Schema& schema, bool zero_terms_all = false,
+                            uint32_t slop = 0) {
     const SchemaField* f = schema.field(field);
     if (!f || f->type != "text")
         throw std::runtime_error("phrase on unknown/non-text field: " + field);
@@ -506,8 +521,72 @@ inline PlanNode phrase_plan(const std::string& field, const std::string& text,
     n.kind = PlanNode::PHRASE;
     n.field = field;
     n.phrase_toks = std::move(toks);
+    n.slop = slop;
     return n;
 }
+
+#ifdef QW_PHRASE_WINDOW
+// one token as an (uncapped) term prefix: the wildcard path
+inline PlanNode term_prefix_plan(const std::string& field,
+                                 const std::string& tok) {
+    if (tok.find('*') != std::string::npos || tok.find('?') != std::string::npos)
+        throw std::runtime_error("phrase prefix with wildcard metachars");
+    PlanNode n;
+    n.kind = PlanNode::WILDCARD;
+    n.const_score = true;
+    n.field = field;
+    n.value = tok + "*";
+    return n;
+}
+
+// phrase_prefix AST (query_ast/phrase_prefix_query.rs): the last token is a
+// prefix capped at max_expansions dictionary terms; a single token is an
+// uncapped prefix (ibid. :104-114); slop is ignored.
+inline PlanNode phrase_prefix_plan(const mj::Value* ast, const Schema& schema) {
+    const std::string& field = ast->at("field")->s;
+    PlanNode n;
+    const SchemaField* f = schema.field(field);
+    if (!f) {
+        const mj::Value* len = ast->get("lenient");
+        if (len && len->b) {
+            n.kind = PlanNode::MATCH_NONE;
+            return n;
+        }
+        throw std::runtime_error("phrase_prefix on unknown field: " + field);
+    }
+    if (f->type != "text")
+        throw std::runtime_error("phrase_prefix on non-text field: " + field);
+    std::string tokenizer = f->tokenizer;
+    bool zta = false;
+    if (const mj::Value* params = ast->get("params")) {
+        const mj::Value* z = params->get("zero_terms_query");
+        zta = z && z->s == "all";
+        const mj::Value* tk = params->get("tokenizer");
+        if (tk && !tk->is_null()) {
+            if (tk->s != "raw" && tk->s != "default")
+                throw std::runtime_error("unknown tokenizer: " + tk->s);
+            tokenizer = tk->s;
+        }
+    }
+    std::vector<std::string> toks = tokenize(ast->at("phrase")->s, tokenizer);
+    if (toks.empty()) {
+        n.kind = zta ? PlanNode::MATCH_ALL : PlanNode::MATCH_NONE;
+        return n;
+    }
+    if (toks.size() == 1) return term_prefix_plan(field, toks[0]);
+    n.kind = PlanNode::PHRASE;
+    n.field = field;
+    n.phrase_toks = std::move(toks);
+    n.prefix_last = true;
+    const mj::Value* me = ast->get("max_expansions");
+    if (me && !me->is_null()) {
+        int64_t v = me->as_i64();
+        if (v < 0) throw std::runtime_error("max_expansions must be >= 0");
+        n.max_expansions = uint32_t(std::min<int64_t>(v, UINT32_MAX));
+    }
+    return n;
+}
+#endif
 
 // minimal user_input support: whitespace-separated clauses of `field:token`
 // or bare tokens over default fields, implicit OR (the subset quickwit's
@@ -519,7 +598,8 @@ inline PlanNode phrase_plan(const std::string& field, const std::string& text,
 // golden scenarios): clause sequences with +/-/NOT prefixes and AND/OR
 // connectors, parentheses, `*`, field:*, field:value, field:"quoted",
 // field:[a TO b] / {a TO b}, field:>=v >v <=v <v, field:IN [a b], ^boost.
-// Out of scope r1: regex //, slop ~N, multi-token phrases (need positions).
+// Out of scope: regex //. Slop "a b"~N and multi-token "a b c"* are accepted
+// by the product build only (QW_PHRASE_WINDOW).
 struct QTok {
     enum Kind { LPAREN, RPAREN, AND, OR, NOT, PLUS, MINUS, LIT } kind = LIT;
     std::string field;   // LIT: optional field ("" = default fields)
@@ -527,6 +607,7 @@ struct QTok {
     bool quoted = false;
     bool no_glob = false;  // backslash-escaped * or ? (literal, not glob)
     bool prefix = false;  // quoted phrase followed by '*' (phrase prefix)
+    uint32_t slop = 0;    // quoted phrase followed by '~N' (product build)
     bool range_ge = false, range_gt = false, range_le = false, range_lt = false;
     bool bracket = false;  // [a TO b] / {a TO b}
     bool lo_incl = true, hi_incl = true;
@@ -552,6 +633,20 @@ inline std::vector<QTok> qlex(const std::string& s) {
         }
         return false;
     };
+    auto after_quote_slop = [&]() -> uint32_t {  // "phrase"~N -> slop N
+#ifdef QW_PHRASE_WINDOW
+        if (i + 1 < s.size() && s[i] == '~' &&
+            isdigit((unsigned char)s[i + 1])) {
+            ++i;
+            uint64_t v = 0;
+            while (i < s.size() && isdigit((unsigned char)s[i]))
+                v = std::min<uint64_t>(v * 10 + uint64_t(s[i++] - '0'),
+                                       UINT32_MAX);
+            return uint32_t(v);
+        }
+#endif
+        return 0;
+    };
     while (i < s.size()) {
         char c = s[i];
         if (c == ' ' || c == '\t') { ++i; continue; }
@@ -571,6 +666,7 @@ inline std::vector<QTok> qlex(const std::string& s) {
             read_quoted(&t.text, c);
             t.quoted = true;
             t.prefix = after_quote_star();
+            if (!t.prefix) t.slop = after_quote_slop();
         } else {
             bool esc = false;
             while (i < s.size() && s[i] != ' ' && s[i] != '\t' && s[i] != '(' &&
@@ -590,6 +686,7 @@ inline std::vector<QTok> qlex(const std::string& s) {
                     read_quoted(&t.text, s[i]);
                     t.quoted = true;
                     t.prefix = after_quote_star();
+                    if (!t.prefix) t.slop = after_quote_slop();
                 } else if (i < s.size() && (s[i] == '[' || s[i] == '{')) {
                     t.bracket = true;
                     t.lo_incl = s[i] == '[';
@@ -871,9 +968,20 @@ inline PlanNode qtok_leaf_impl(const QTok& t, const std::vector<std::string>& df
             if (t.prefix) {
                 // "phrase"* phrase-prefix: supported where it reduces to a
                 // single-token prefix (e.g. raw tokenizer), as a wildcard
+#ifdef QW_PHRASE_WINDOW
+                if (toks.size() != 1) {  // "a b c"*: capped at 50 expansions
+                    n.kind = PlanNode::PHRASE;
+                    n.field = t.field;
+                    n.phrase_toks = std::move(toks);
+                    n.prefix_last = true;
+                    n.boost = t.boost;
+                    return n;
+                }
+#else
                 if (toks.size() != 1)
                     throw std::runtime_error(
                         "multi-token phrase prefix not supported");
+#endif
                 if (toks[0].find('*') != std::string::npos ||
                     toks[0].find('?') != std::string::npos)
                     throw std::runtime_error(
@@ -889,6 +997,7 @@ inline PlanNode qtok_leaf_impl(const QTok& t, const std::vector<std::string>& df
                 n.kind = PlanNode::PHRASE;
                 n.field = t.field;
                 n.phrase_toks = std::move(toks);
+                n.slop = t.slop;  // "a b"~N
                 n.boost = t.boost;
                 return n;
             }
@@ -980,6 +1089,18 @@ inline PlanNode qtok_leaf_impl(const QTok& t, const std::vector<std::string>& df
         // dynamic fields absent from a given split's schema
         const SchemaField* f = schema.field(df);
         if (!f) continue;
+#ifdef QW_PHRASE_WINDOW
+        // "a b"~N / "a b c"* over a default text field: that field's
+        // sloppy phrase / phrase prefix
+        if (t.quoted && f->type == "text" &&
+            (t.slop || (t.prefix && tokenize(t.text, f->tokenizer).size() > 1))) {
+            QTok ft = t;
+            ft.field = df;
+            ft.boost = 1.0f;
+            b.should.push_back(qtok_leaf_impl(ft, dfs_in, schema));
+            continue;
+        }
+#endif
         if (f->type != "text") {
             // numeric/bool/str fast default field: equality when the
             // literal parses for that type (lenient otherwise)
@@ -1052,11 +1173,19 @@ inline PlanNode build_plan(const mj::Value* ast, const Schema& schema) {
                 const mj::Value* mt = mode->get("type");
                 if (mt && mt->s == "phrase") {
                     const mj::Value* slop = mode->get("slop");
+#ifdef QW_PHRASE_WINDOW
+                    int64_t sl = slop && !slop->is_null() ? slop->as_i64() : 0;
+                    if (sl < 0) throw std::runtime_error("phrase slop < 0");
+                    return phrase_plan(
+                        ast->at("field")->s, ast->at("text")->s, schema, zta,
+                        uint32_t(std::min<int64_t>(sl, UINT32_MAX)));
+#else
                     if (slop && slop->as_i64() != 0)
                         throw std::runtime_error(
                             "phrase slop > 0 not supported (r2 limit)");
                     return phrase_plan(ast->at("field")->s,
                                        ast->at("text")->s, schema, zta);
+#endif
                 }
                 if (mt && mt->s != "bool" && mt->s != "bool_prefix")
                     throw std::runtime_error("full_text mode not supported: " + mt->s);
@@ -1135,6 +1264,10 @@ inline PlanNode build_plan(const mj::Value* ast, const Schema& schema) {
         // field's tokenizer (wildcard_query.rs:111-160): for the default
         // (lowercasing) analyzer that lowercases them
         if (f->tokenizer != "raw") n.value = qw_utf8_lower(n.value);
+#ifdef QW_PHRASE_WINDOW
+    } else if (ty == "phrase_prefix") {
+        return phrase_prefix_plan(ast, schema);
+#endif
     } else if (ty == "user_input") {
         std::vector<std::string> dfs;
         const mj::Value* d = ast->get("default_fields");

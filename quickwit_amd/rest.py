@@ -72,7 +72,15 @@ def _parse_java_date(fmt, s):
 
 # -------------------------------------------------- ES query DSL -> QueryAst
 # (quickwit-query/src/elastic_query_dsl/ subset the scenario suites use)
-def es_query_to_ast(q, schema=None):
+def es_query_to_ast(q, schema=None, lenient=False):
+    """`lenient` reaches only the forms that carry it in their AST (a
+    multi_match expanding into per-field phrase prefixes)."""
+    def text_tokenizer(name):
+        for f in (schema or {}).get("fields", []):
+            if f["name"] == name and f["type"] == "text":
+                return f.get("tokenizer", "default")
+        return "default"
+
     def numeric_field(name):
         for f in (schema or {}).get("fields", []):
             if f["name"] == name and f["type"] in ("u64", "i64", "f64"):
@@ -151,10 +159,25 @@ def es_query_to_ast(q, schema=None):
     if "match_phrase_prefix" in q:
         [(field, body)] = q["match_phrase_prefix"].items()
         text = str(body["query"] if isinstance(body, dict) else body).strip()
-        if " " in text:
-            raise ValueError(
-                "multi-token match_phrase_prefix not supported")
+        params = body if isinstance(body, dict) else {}
+        analyzer = params.get("analyzer")
+        if analyzer is not None and analyzer not in ("raw", "default"):
+            raise ValueError(f"unknown tokenizer: {analyzer}")
+        from .splitgen import tokenize
+        if len(tokenize(text, analyzer or text_tokenizer(field))) > 1:
+            # several tokens: the last one is a prefix capped at
+            # max_expansions dictionary terms (phrase_prefix_query.rs); slop
+            # is ignored on phrase prefixes
+            fparams = {"mode": {"type": "phrase"}}
+            if analyzer is not None:
+                fparams["tokenizer"] = analyzer
+            if "zero_terms_query" in params:
+                fparams["zero_terms_query"] = params["zero_terms_query"]
+            return {"type": "phrase_prefix", "field": field, "phrase": text,
+                    "max_expansions": int(params.get("max_expansions", 50)),
+                    "params": fparams, "lenient": lenient}
         # single analyzed token: phrase prefix == term prefix == wildcard
+        # (uncapped, phrase_prefix_query.rs:104-114)
         if "*" in text or "?" in text:
             raise ValueError("phrase prefix with wildcard metachars")
         return {"type": "wildcard", "field": field, "value": text + "*"}
@@ -262,7 +285,8 @@ def es_query_to_ast(q, schema=None):
                 "default_fields": dfs}
     if "multi_match" in q:
         # unknown fields contribute nothing (ES semantics, regardless of
-        # lenient); slop and multi-token phrase_prefix are declared out
+        # lenient); type phrase (with slop) and phrase_prefix expand into
+        # the per-field match_phrase / match_phrase_prefix forms
         body = q["multi_match"]
         fields = body.get("fields")
         if isinstance(fields, str):  # ES accepts a single-string fields
@@ -270,18 +294,22 @@ def es_query_to_ast(q, schema=None):
         if not fields:
             raise ValueError("multi_match requires a non-empty fields list")
         mtype = body.get("type", "best_fields")
-        if body.get("slop"):
-            raise ValueError("multi_match slop > 0 not supported")
-        if mtype == "phrase_prefix":
-            raise ValueError("multi_match phrase_prefix not supported")
+        if body.get("slop") and mtype != "phrase":
+            raise ValueError("multi_match slop needs type phrase")
         known = {f["name"] for f in (schema or {}).get("fields", [])}
         use = [f for f in fields if f in known] if schema else fields
+        # the per-field parameters: everything but the multi_match's own keys
+        per_field = {k: v for k, v in body.items()
+                     if k not in ("type", "fields", "lenient")}
         subs = []
         for f in use:
             if mtype == "phrase":
-                subs.append({"type": "full_text", "field": f,
-                             "text": str(body["query"]),
-                             "params": {"mode": {"type": "phrase"}}})
+                subs.append(es_query_to_ast(
+                    {"match_phrase": {f: per_field}}, schema))
+            elif mtype == "phrase_prefix":
+                subs.append(es_query_to_ast(
+                    {"match_phrase_prefix": {f: per_field}}, schema,
+                    lenient=bool(body.get("lenient", False))))
             else:
                 op = str(body.get("operator", "or")).lower()
                 subs.append({"type": "full_text", "field": f,
