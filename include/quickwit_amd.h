@@ -119,6 +119,32 @@ int32_t qw_finalize_agg_to_json(const uint8_t* blob, size_t len,
                                 const char* agg_request_json,
                                 qw_buf* json_out);
 
+/* Regex over a packed term list, on the host, without a ctx or a GPU: the
+ * same byte DFA (csrc/qregex.h) a regex query scans a split's dictionary
+ * with on the device. Term t is term_bytes[term_offsets[t] ..
+ * term_offsets[t+1]); term_offsets has num_terms + 1 entries. Sets bit t % 64
+ * of match_bitmap_out[t / 64] iff the WHOLE term matches; the caller provides
+ * (num_terms + 63) / 64 words, all of which are written. The regex is taken
+ * as given (no automatic "(?i)"). A refused or malformed regex returns
+ * QW_ERR_INVALID_QUERY with the construct named in qw_last_error(NULL). */
+int32_t qw_regex_match_terms(const char* regex, size_t regex_len,
+                             const uint8_t* term_bytes,
+                             const uint32_t* term_offsets, size_t num_terms,
+                             uint64_t* match_bitmap_out);
+
+/* Size of the DFA a regex compiles to: out[0] = states (dead state
+ * included), out[1] = byte classes, out[2] = bytes of the table image the
+ * device reads (k_dict_dfa_match stages it in LDS up to 64 KB and reads it
+ * from global memory above). Errors as qw_regex_match_terms. */
+int32_t qw_regex_table_stats(const char* regex, size_t regex_len,
+                             uint64_t out[3]);
+
+/* The regex a regex query on a field evaluates: "(?i)" is prepended when the
+ * field's tokenizer lowercases, unless a leading flag group already carries
+ * `i` (RegexQuery::to_resolved, query_ast/regex_query.rs). */
+int32_t qw_regex_resolve(const char* regex, size_t regex_len,
+                         int32_t tokenizer_lowercases, qw_buf* resolved_out);
+
 /* Last error message for this ctx (UTF-8, valid until next call on ctx).
  * For ctx-less entry points (merge/finalize), pass NULL to read the
  * thread-local message. */
@@ -129,7 +155,8 @@ const char* qw_last_error(const qw_ctx* ctx);
 /* Accumulated device time (HIP events on the launch stream) and launch count
  * for a named kernel since the last reset. Returns QW_ERR_NOT_FOUND for an
  * unknown name. Known names: "union_bm25", "range_filter", "column_agg",
- * "topk_select". */
+ * "topk_select", "k_dict_dfa_match", "k_terms_union_bitmap" (the two regex
+ * kernels; other kernels appear under their own names once launched). */
 int32_t qw_kernel_stats(qw_ctx* ctx, const char* kernel_name,
                         double* total_ms, uint64_t* launches);
 void qw_kernel_stats_reset(qw_ctx* ctx);

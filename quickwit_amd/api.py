@@ -217,6 +217,83 @@ class GpuSearcher(_BaseSearcher):
             raise RuntimeError(f"device_sync failed: {self._err()}")
 
 
+# ------------------------------------------------------------------ regex
+def _product_lib():
+    path = os.environ.get("QW_PRODUCT_LIB") or os.path.join(
+        REPO_ROOT, "libquickwit_amd.so")
+    if not os.path.exists(path):
+        raise FileNotFoundError(
+            f"{path} not built — run __graft_entry__.build() first")
+    lib = ctypes.CDLL(path)
+    lib.qw_last_error.restype = ctypes.c_char_p
+    lib.qw_last_error.argtypes = [ctypes.c_void_p]
+    return lib
+
+
+def regex_match_terms(regex: str | bytes, terms: list) -> list:
+    """Host run of the regex byte DFA (csrc/qregex.h, the one the device
+    scans a split's dictionary with) over `terms` (str or bytes each): one
+    bool per term, True iff the whole term matches. Needs no GPU. The regex
+    is taken as given; a refused or malformed one raises ValueError naming
+    the construct."""
+    lib = _product_lib()
+    raw = [t.encode() if isinstance(t, str) else bytes(t) for t in terms]
+    offsets = (ctypes.c_uint32 * (len(raw) + 1))()
+    pos = 0
+    for i, t in enumerate(raw):
+        offsets[i] = pos
+        pos += len(t)
+    offsets[len(raw)] = pos
+    packed = b"".join(raw)
+    words = (ctypes.c_uint64 * max(1, (len(raw) + 63) // 64))()
+    rx = regex.encode() if isinstance(regex, str) else bytes(regex)
+    fn = lib.qw_regex_match_terms
+    fn.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
+                   ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t,
+                   ctypes.POINTER(ctypes.c_uint64)]
+    rc = fn(rx, len(rx), packed, offsets, len(raw), words)
+    if rc != 0:
+        msg = lib.qw_last_error(None)
+        raise ValueError(msg.decode(errors="replace") if msg else f"rc={rc}")
+    return [bool((words[i >> 6] >> (i & 63)) & 1) for i in range(len(raw))]
+
+
+def regex_table_stats(regex: str | bytes) -> tuple:
+    """(states, byte classes, table bytes) of the DFA `regex` compiles to;
+    the table is what the device scan reads (LDS up to 64 KB, global memory
+    above). Raises ValueError like regex_match_terms."""
+    lib = _product_lib()
+    fn = lib.qw_regex_table_stats
+    fn.argtypes = [ctypes.c_char_p, ctypes.c_size_t,
+                   ctypes.POINTER(ctypes.c_uint64 * 3)]
+    rx = regex.encode() if isinstance(regex, str) else bytes(regex)
+    out = (ctypes.c_uint64 * 3)()
+    rc = fn(rx, len(rx), ctypes.byref(out))
+    if rc != 0:
+        msg = lib.qw_last_error(None)
+        raise ValueError(msg.decode(errors="replace") if msg else f"rc={rc}")
+    return tuple(out)
+
+
+def regex_resolve(regex: str, tokenizer_lowercases: bool) -> str:
+    """The regex a regex query evaluates on a field: "(?i)" prepended when
+    the field's tokenizer lowercases, unless a leading flag group already
+    carries `i` (RegexQuery::to_resolved)."""
+    lib = _product_lib()
+    fn = lib.qw_regex_resolve
+    fn.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int32,
+                   ctypes.POINTER(_Buf)]
+    rx = regex.encode()
+    buf = _Buf()
+    rc = fn(rx, len(rx), int(bool(tokenizer_lowercases)), ctypes.byref(buf))
+    if rc != 0:
+        raise RuntimeError(f"regex_resolve failed ({rc})")
+    out = ctypes.string_at(buf.data, buf.len).decode()
+    lib.qw_buf_free.argtypes = [ctypes.POINTER(_Buf)]
+    lib.qw_buf_free(ctypes.byref(buf))
+    return out
+
+
 # ---------------------------------------------------------------- helpers
 def make_leaf_request(query_ast: dict | str, schema: dict, splits: list,
                       max_hits: int = 10, sort_fields: list | None = None,

@@ -1712,4 +1712,124 @@ k_phrase_window_bitmap(const uint8_t* split, PhraseDev p,
     }
 }
 
+// -------------------------------------------------------------- regex eval
+// A regex query (PlanNode::REGEX) is two launches: the byte DFA of qregex.h
+// runs over every term of the field's dictionary, then the posting lists of
+// the matched terms are ORed into a HitSet bitmap. DESIGN.md §7.
+//
+// DFA table image, built by the host (dfa_table_image in product.cpp):
+//   [0, 256)                          class_of, u8 per byte value
+//   [256, 256 + 2 * S * C)            next, u16; state 0 dead, state 1 start
+//   [accept_off, accept_off + 8 * ceil(S/64))   accept bitset, u64 words
+// accept_off is 8-aligned and table_bytes a multiple of 8.
+struct DfaDev {
+    const uint8_t* table;  // device copy of the image
+    uint32_t n_classes;
+    uint32_t accept_off;
+    uint32_t table_bytes;
+    uint32_t in_lds;  // stage the image in dynamic LDS (table_bytes of it)
+};
+
+// One lane per term, one wave per 64 consecutive terms = one word of the
+// match bitmap (ceil(num_terms/64) words, each written exactly once, by a
+// plain store of the wave's ballot; lanes past num_terms vote 0).
+extern "C" __global__ void __launch_bounds__(256)
+k_dict_dfa_match(const uint8_t* split, uint64_t term_offsets_off,
+                 uint64_t term_bytes_off, uint32_t num_terms, DfaDev d,
+                 uint64_t* match) {
+    extern __shared__ uint64_t dfa_lds[];
+    const uint8_t* tab = d.table;
+    if (d.in_lds) {
+        const uint64_t* src = (const uint64_t*)d.table;
+        for (uint32_t i = threadIdx.x; i < d.table_bytes / 8; i += blockDim.x)
+            dfa_lds[i] = src[i];
+        __syncthreads();
+        tab = (const uint8_t*)dfa_lds;
+    }
+    const uint8_t* class_of = tab;
+    const uint16_t* next = (const uint16_t*)(tab + 256);
+    const uint64_t* accept = (const uint64_t*)(tab + d.accept_off);
+    const uint32_t* offs = (const uint32_t*)(split + term_offsets_off);
+    const uint8_t* bytes = split + term_bytes_off;
+    const uint32_t n_words = (num_terms + 63u) / 64u;
+    const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint32_t n_waves = gridDim.x * (blockDim.x >> 6);
+    for (uint32_t w = wave; w < n_words; w += n_waves) {  // wave-uniform
+        const uint32_t t = w * 64u + lane_id();
+        bool m = false;
+        if (t < num_terms) {
+            uint32_t st = 1;
+            const uint32_t end = offs[t + 1];
+            for (uint32_t i = offs[t]; i < end && st; ++i)
+                st = next[st * d.n_classes + class_of[bytes[i]]];
+            m = (accept[st >> 6] >> (st & 63u)) & 1ull;
+        }
+        const uint64_t votes = __ballot(m);
+        if (lane_id() == 0) match[w] = votes;
+    }
+}
+
+// gap field j of a block's w-bit gap section; reads the second word only
+// when the field crosses into it (never past the section)
+__device__ __forceinline__ uint32_t union_gap(const uint32_t* gw, uint32_t j,
+                                              uint32_t w) {
+    if (!w) return 0;  // empty gap section: nothing to load
+    const uint32_t bit = j * w, word = bit >> 5, sh = bit & 31u;
+    uint64_t v = gw[word];
+    if (sh + w > 32u) v |= uint64_t(gw[word + 1]) << 32;
+    return uint32_t(v >> sh) & (w >= 32u ? 0xFFFFFFFFu : (1u << w) - 1u);
+}
+
+// One wave per (matched term, 128-doc skip block): `terms` lists the matched
+// term ids, blk_prefix[k] the number of blocks of terms[0..k) (n_terms + 1
+// entries, the last = total_blocks). Lane l decodes postings 2l and 2l+1:
+// doc ids come back from first_doc and the block's three 32-posting anchors
+// (layout: phrase_doc_at) by a prefix sum inside each 16-lane segment. The
+// bitmap must be zero before the launch.
+extern "C" __global__ void __launch_bounds__(256)
+k_terms_union_bitmap(const uint8_t* split, uint64_t skip_off_tab_off,
+                     uint64_t skip_off, uint64_t payload_off,
+                     const uint32_t* terms, const uint32_t* blk_prefix,
+                     uint32_t n_terms, uint32_t total_blocks, uint32_t num_docs,
+                     uint32_t* bitmap) {
+    const uint32_t lane = lane_id();
+    const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint32_t n_waves = gridDim.x * (blockDim.x >> 6);
+    const uint64_t* skip_off_tab = (const uint64_t*)(split + skip_off_tab_off);
+    const uint32_t* payload = (const uint32_t*)(split + payload_off);
+    for (uint32_t g = wave; g < total_blocks; g += n_waves) {  // wave-uniform
+        // last k with blk_prefix[k] <= g (terms without blocks are skipped)
+        uint32_t lo = 0, hi = n_terms;
+        while (hi - lo > 1) {
+            uint32_t mid = (lo + hi) >> 1;
+            if (blk_prefix[mid] <= g) lo = mid;
+            else hi = mid;
+        }
+        const uint32_t tid = terms[lo];
+        const SkipEntryDev* skip =
+            (const SkipEntryDev*)(split + skip_off + skip_off_tab[tid]);
+        const SkipEntryDev e = skip[g - blk_prefix[lo]];
+        const uint32_t* gw = payload + e.word_off;
+        const uint32_t j0 = 2u * lane, j1 = j0 + 1u, seg = lane >> 4;
+        const uint32_t count = e.count < 128u ? e.count : 128u;
+        uint32_t g0 = 0, g1 = 0, base = e.first_doc;
+        if (j0 < count) {
+            if (j0) g0 = union_gap(gw, j0, e.id_bits);  // posting 0 = first_doc
+            if (seg) base = (gw - 4)[seg];  // doc of posting 32 * seg - 1
+        }
+        if (j1 < count) g1 = union_gap(gw, j1, e.id_bits);
+        uint32_t sum = g0 + g1;
+        #pragma unroll
+        for (int dlt = 1; dlt < 16; dlt <<= 1) {
+            uint32_t n = __shfl_up(sum, dlt, 16);
+            if ((lane & 15u) >= uint32_t(dlt)) sum += n;
+        }
+        const uint32_t doc1 = base + sum, doc0 = doc1 - g1;
+        if (j0 < count && doc0 < num_docs)
+            atomicOr(&bitmap[doc0 >> 5], 1u << (doc0 & 31u));
+        if (j1 < count && doc1 < num_docs)
+            atomicOr(&bitmap[doc1 >> 5], 1u << (doc1 & 31u));
+    }
+}
+
 }  // namespace qw

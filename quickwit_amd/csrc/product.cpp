@@ -37,6 +37,9 @@
 // here: the CPU oracle shares qast.h and has no evaluator for them, so it
 // keeps refusing them (defined before the first include that pulls qast.h in)
 #define QW_PHRASE_WINDOW 1
+// likewise regex queries (PlanNode::REGEX, the regex AST type and the
+// field:/re/ literal)
+#define QW_REGEX_QUERY 1
 
 #include "../../include/quickwit_amd.h"
 #include "fieldnorm.h"
@@ -695,6 +698,9 @@ static void add_positive(FlatQuery& fq, const SplitView& sv, const PlanNode& c,
         case PlanNode::PHRASE:
             throw std::runtime_error(
                 "phrase clause not flattenable (device-bitmap path)");
+        case PlanNode::REGEX:
+            throw std::runtime_error(
+                "regex clause not flattenable (device-bitmap path)");
     }
 }
 
@@ -803,11 +809,14 @@ static FlatQuery flatten(const SplitView& sv, const PlanNode& plan, bool scoring
     fq.scoring = scoring;
     if (scoring && plan_has_const_score(plan))
         throw std::runtime_error(
-            "term_set/wildcard/phrase under _score sorting not supported "
+            "term_set/wildcard/phrase/regex under _score sorting not supported "
             "(const-score semantics, qast.h)");
     if (plan.kind == PlanNode::PHRASE)
         throw std::runtime_error(
             "phrase not flattenable (device-bitmap path)");
+    if (plan.kind == PlanNode::REGEX)
+        throw std::runtime_error(
+            "regex not flattenable (device-bitmap path)");
     switch (plan.kind) {
         case PlanNode::MATCH_ALL:
             fq.match_all = true;
@@ -1437,6 +1446,104 @@ static uint8_t* bitmap_eval(qw_ctx* ctx, const DeviceSplit& ds,
     return bm;
 }
 
+// host image of a DFA in the layout k_dict_dfa_match reads (kernels.hip)
+static std::vector<uint8_t> dfa_table_image(const rx::Dfa& dfa, DfaDev* d) {
+    size_t next_bytes = dfa.next.size() * 2;
+    size_t accept_off = dfa.accept_off();
+    std::vector<uint8_t> img(dfa.table_bytes(), 0);
+    memcpy(img.data(), dfa.class_of, 256);
+    memcpy(img.data() + 256, dfa.next.data(), next_bytes);
+    memcpy(img.data() + accept_off, dfa.accept.data(), dfa.accept.size() * 8);
+    d->n_classes = dfa.n_classes;
+    d->accept_off = uint32_t(accept_off);
+    d->table_bytes = uint32_t(img.size());
+    d->in_lds = img.size() <= 64 * 1024 ? 1u : 0u;
+    return img;
+}
+
+// PlanNode::REGEX into the (allocated, not yet zeroed) bitmap `bm`
+static void regex_hitset(qw_ctx* ctx, const DeviceSplit& ds, const PlanNode& n,
+                         uint8_t* bm, size_t bm_bytes) {
+    const SplitView& sv = ds.view;
+    const TextFieldView* f = sv.text_field(n.field);
+    HIP_CHECK(hipMemsetAsync(bm, 0, bm_bytes, ctx->stream));
+    if (!f || !f->num_terms) {  // no such text field in this split: no hits
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        return;
+    }
+    // memoised: planned once, evaluated once per split and segment
+    std::shared_ptr<const rx::Dfa> dfa = rx::compile_cached(n.value);
+    DfaDev dd{};
+    std::vector<uint8_t> img = dfa_table_image(*dfa, &dd);
+
+    // 1. DFA scan: scratch = table image | match words
+    const uint32_t n_words = (f->num_terms + 63u) / 64u;
+    const size_t match_off = img.size();  // multiple of 8
+    qw_ensure_acct(ctx, ctx->d_scratch, match_off + size_t(n_words) * 8);
+    HIP_CHECK(hipMemcpyAsync(ctx->d_scratch.p, img.data(), img.size(),
+                             hipMemcpyHostToDevice, ctx->stream));
+    dd.table = ctx->d_scratch.p;
+    uint64_t* d_match = (uint64_t*)(ctx->d_scratch.p + match_off);
+    {
+        // 4 words per 256-thread block; the kernel strides over the rest, so
+        // a staged table is loaded at most 1024 times
+        uint32_t grid = std::min<uint32_t>(1024u, (n_words + 3u) / 4u);
+        HIP_CHECK(hipEventRecord(ctx->ev_start, ctx->stream));
+        hipLaunchKernelGGL(k_dict_dfa_match, dim3(grid), dim3(256),
+                           dd.in_lds ? dd.table_bytes : 0u, ctx->stream,
+                           ds.d_image, f->term_offsets.off, f->term_bytes.off,
+                           f->num_terms, dd, d_match);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(ctx->ev_stop, ctx->stream));
+    }
+    // 2. read back (num_terms / 8 bytes)
+    std::vector<uint64_t> match(n_words);
+    HIP_CHECK(hipMemcpyAsync(match.data(), d_match, size_t(n_words) * 8,
+                             hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    {
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+        record_kernel_time(ctx, "k_dict_dfa_match", ms);
+    }
+    // 3. matched-term list + exclusive prefix of their block counts
+    std::vector<uint32_t> up;  // terms[n] | blk_prefix[n + 1]
+    std::vector<uint32_t> prefix(1, 0u);
+    uint64_t total = 0;
+    for (uint32_t w = 0; w < n_words; ++w)
+        for (uint64_t bits = match[w]; bits; bits &= bits - 1) {
+            uint32_t t = w * 64u + uint32_t(__builtin_ctzll(bits));
+            if (t >= f->num_terms || !f->h_n_blocks[t]) continue;
+            up.push_back(t);
+            total += f->h_n_blocks[t];
+            if (total > UINT32_MAX)
+                throw std::runtime_error(
+                    "regex matches more than 2^32 posting blocks");
+            prefix.push_back(uint32_t(total));
+        }
+    if (up.empty()) return;  // nothing matched: the zeroed bitmap stands
+    // 4. union
+    const uint32_t n_matched = uint32_t(up.size());
+    up.insert(up.end(), prefix.begin(), prefix.end());
+    qw_ensure_acct(ctx, ctx->d_scratch, up.size() * 4);
+    HIP_CHECK(hipMemcpyAsync(ctx->d_scratch.p, up.data(), up.size() * 4,
+                             hipMemcpyHostToDevice, ctx->stream));
+    const uint32_t* d_terms = (const uint32_t*)ctx->d_scratch.p;
+    uint32_t grid =
+        uint32_t(std::min<uint64_t>(2048u, (total + 3u) / 4u));  // wave each
+    HIP_CHECK(hipEventRecord(ctx->ev_start, ctx->stream));
+    hipLaunchKernelGGL(k_terms_union_bitmap, dim3(grid), dim3(256), 0,
+                       ctx->stream, ds.d_image, f->skip_off.off, f->skip.off,
+                       f->payload.off, d_terms, d_terms + n_matched, n_matched,
+                       uint32_t(total), sv.num_docs, (uint32_t*)bm);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(ctx->ev_stop, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+    record_kernel_time(ctx, "k_terms_union_bitmap", ms);
+}
+
 static uint8_t* resolve_hitset(qw_ctx* ctx, const DeviceSplit& ds,
                                const PlanNode& inner, const Schema& schema) {
     const SplitView& sv = ds.view;
@@ -1576,6 +1683,20 @@ static uint8_t* resolve_hitset(qw_ctx* ctx, const DeviceSplit& ds,
             float ms = 0;
             HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
             record_kernel_time(ctx, kname, ms);
+        }
+        ctx->hitsets.put(key, bm, bm_bytes);
+        return bm;
+    }
+
+    if (inner.kind == PlanNode::REGEX) {
+        // regex (regex_query.rs -> AutomatonQuery): compile, DFA scan of the
+        // field's dictionary on the device, read the per-term match bitmap
+        // back, union the matched terms' postings — no cap on their number
+        try {
+            regex_hitset(ctx, ds, inner, bm, bm_bytes);
+        } catch (...) {
+            (void)hipFree(bm);
+            throw;
         }
         ctx->hitsets.put(key, bm, bm_bytes);
         return bm;
@@ -3402,7 +3523,10 @@ int32_t qw_leaf_search(qw_ctx* ctx, const uint8_t* req_pb, size_t req_len,
         set_err(ctx, e.what());
         std::string msg = e.what();
         if (msg.find("not supported") != std::string::npos ||
-            msg.find("not flattenable") != std::string::npos)
+            msg.find("not flattenable") != std::string::npos ||
+            msg.find("invalid regex") != std::string::npos ||
+            msg.find("regex on unknown field") != std::string::npos ||
+            msg.find("regex query on a non-text field") != std::string::npos)
             return QW_ERR_INVALID_QUERY;
         return QW_ERR_INTERNAL;
     }
@@ -3670,12 +3794,77 @@ int32_t qw_finalize_agg_to_json(const uint8_t* blob, size_t len,
     }
 }
 
+int32_t qw_regex_match_terms(const char* regex, size_t regex_len,
+                             const uint8_t* term_bytes,
+                             const uint32_t* term_offsets, size_t num_terms,
+                             uint64_t* match_bitmap_out) {
+    using namespace qw;
+    try {
+        if (!regex || !term_offsets || !match_bitmap_out ||
+            (num_terms && !term_bytes && term_offsets[num_terms])) {
+            set_err(nullptr, "qw_regex_match_terms: null argument");
+            return QW_ERR_INVALID_ARGUMENT;
+        }
+        std::shared_ptr<const rx::Dfa> cached =
+            rx::compile_cached(std::string(regex, regex_len));
+        const rx::Dfa& dfa = *cached;
+        for (size_t w = 0; w < (num_terms + 63) / 64; ++w) {
+            uint64_t bits = 0;
+            for (size_t t = w * 64; t < std::min(num_terms, w * 64 + 64); ++t)
+                if (rx::match(dfa, term_bytes + term_offsets[t],
+                              term_offsets[t + 1] - term_offsets[t]))
+                    bits |= 1ull << (t & 63);
+            match_bitmap_out[w] = bits;
+        }
+        return QW_OK;
+    } catch (const std::exception& e) {
+        set_err(nullptr, e.what());
+        return QW_ERR_INVALID_QUERY;
+    }
+}
+
+int32_t qw_regex_table_stats(const char* regex, size_t regex_len,
+                             uint64_t out[3]) {
+    try {
+        if (!regex || !out) {
+            set_err(nullptr, "qw_regex_table_stats: null argument");
+            return QW_ERR_INVALID_ARGUMENT;
+        }
+        std::shared_ptr<const qw::rx::Dfa> dfa =
+            qw::rx::compile_cached(std::string(regex, regex_len));
+        out[0] = dfa->n_states;
+        out[1] = dfa->n_classes;
+        out[2] = dfa->table_bytes();
+        return QW_OK;
+    } catch (const std::exception& e) {
+        set_err(nullptr, e.what());
+        return QW_ERR_INVALID_QUERY;
+    }
+}
+
+int32_t qw_regex_resolve(const char* regex, size_t regex_len,
+                         int32_t tokenizer_lowercases, qw_buf* resolved_out) {
+    try {
+        if (!regex || !resolved_out) {
+            set_err(nullptr, "qw_regex_resolve: null argument");
+            return QW_ERR_INVALID_ARGUMENT;
+        }
+        fill_buf(resolved_out, qw::rx::resolve(std::string(regex, regex_len),
+                                               tokenizer_lowercases != 0));
+        return QW_OK;
+    } catch (const std::exception& e) {
+        set_err(nullptr, e.what());
+        return QW_ERR_INTERNAL;
+    }
+}
+
 int32_t qw_kernel_stats(qw_ctx* ctx, const char* kernel_name, double* total_ms,
                         uint64_t* launches) {
     auto it = ctx->timers.find(kernel_name);
     if (it == ctx->timers.end()) {
         static const char* known[] = {"union_bm25", "range_filter", "column_agg",
-                                      "topk_select"};
+                                      "topk_select", "k_dict_dfa_match",
+                                      "k_terms_union_bitmap"};
         bool ok = false;
         for (const char* k : known) ok |= kernel_name == std::string(k);
         if (!ok) return QW_ERR_NOT_FOUND;

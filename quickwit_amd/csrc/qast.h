@@ -31,6 +31,9 @@
 #include "qw_unicode.h"
 
 #include "minijson.h"
+#ifdef QW_REGEX_QUERY
+#include "qregex.h"
+#endif
 
 namespace qw {
 
@@ -190,8 +193,15 @@ struct PlanNode {
     enum Kind {
         MATCH_ALL, MATCH_NONE, TERM, BOOL, RANGE, FIELD_PRESENCE, WILDCARD,
         CACHE, PHRASE
+#ifdef QW_REGEX_QUERY
+        // product build only, like the QW_PHRASE_WINDOW forms: the CPU oracle
+        // shares this header, has no evaluator for it and keeps refusing it
+        , REGEX
+#endif
     } kind = MATCH_ALL;
-    // TERM / WILDCARD (value = glob pattern: '*' any run, '?' one char)
+    // TERM / WILDCARD (value = glob pattern: '*' any run, '?' one char) /
+    // REGEX (value = the resolved regex, any prepended "(?i)" included;
+    // const-score like WILDCARD and PHRASE)
     std::string field;
     std::string value;
     bool ci = false;  // WILDCARD case_insensitive
@@ -266,6 +276,9 @@ inline void plan_fingerprint(const PlanNode& n, std::string& out) {
 // does any node require const-score semantics (term_set / wildcard)?
 inline bool plan_has_const_score(const PlanNode& n) {
     if (n.const_score || n.kind == PlanNode::PHRASE) return true;
+#ifdef QW_REGEX_QUERY
+    if (n.kind == PlanNode::REGEX) return true;
+#endif
     for (auto* v : {&n.must, &n.must_not, &n.should, &n.filter, &n.cache_inner})
         for (auto& c : *v)
             if (plan_has_const_score(c)) return true;
@@ -525,6 +538,27 @@ inline PlanNode phrase_plan(const std::string& field, const std::string& text,
     return n;
 }
 
+#ifdef QW_REGEX_QUERY
+// regex AST / `field:/re/` literal (query_ast/regex_query.rs): the whole term
+// must match; "(?i)" is prepended for a lowercasing tokenizer
+// (RegexQuery::to_resolved). The regex is compiled here once so that a
+// refused construct is an invalid query, not a per-split failure.
+inline PlanNode regex_plan(const std::string& field, const std::string& regex,
+                           const Schema& schema) {
+    const SchemaField* f = schema.field(field);
+    if (!f) throw std::runtime_error("regex on unknown field: " + field);
+    if (f->type != "text")
+        throw std::runtime_error(
+            "trying to run a regex query on a non-text field: " + field);
+    PlanNode n;
+    n.kind = PlanNode::REGEX;
+    n.field = field;
+    n.value = rx::resolve(regex, f->tokenizer != "raw");
+    (void)rx::compile_cached(n.value);
+    return n;
+}
+#endif
+
 #ifdef QW_PHRASE_WINDOW
 // one token as an (uncapped) term prefix: the wildcard path
 inline PlanNode term_prefix_plan(const std::string& field,
@@ -598,8 +632,9 @@ inline PlanNode phrase_prefix_plan(const mj::Value* ast, const Schema& schema) {
 // golden scenarios): clause sequences with +/-/NOT prefixes and AND/OR
 // connectors, parentheses, `*`, field:*, field:value, field:"quoted",
 // field:[a TO b] / {a TO b}, field:>=v >v <=v <v, field:IN [a b], ^boost.
-// Out of scope: regex //. Slop "a b"~N and multi-token "a b c"* are accepted
-// by the product build only (QW_PHRASE_WINDOW).
+// Slop "a b"~N and multi-token "a b c"* are accepted by the product build
+// only (QW_PHRASE_WINDOW), and so is the regex literal field:/re/ (`\/` is a
+// slash inside it; QW_REGEX_QUERY) — without the macro it is refused.
 struct QTok {
     enum Kind { LPAREN, RPAREN, AND, OR, NOT, PLUS, MINUS, LIT } kind = LIT;
     std::string field;   // LIT: optional field ("" = default fields)
@@ -607,6 +642,7 @@ struct QTok {
     bool quoted = false;
     bool no_glob = false;  // backslash-escaped * or ? (literal, not glob)
     bool prefix = false;  // quoted phrase followed by '*' (phrase prefix)
+    bool regex = false;   // /re/ literal: text = the regex, slashes stripped
     uint32_t slop = 0;    // quoted phrase followed by '~N' (product build)
     bool range_ge = false, range_gt = false, range_le = false, range_lt = false;
     bool bracket = false;  // [a TO b] / {a TO b}
@@ -647,6 +683,31 @@ inline std::vector<QTok> qlex(const std::string& s) {
 #endif
         return 0;
     };
+    // /re/ at i: the regex up to the closing unescaped '/', which must end
+    // the literal. `\/` is a slash; every other escape reaches the regex.
+    auto read_regex = [&](std::string* t) -> bool {
+        size_t j = i + 1;
+        std::string re;
+        while (j < s.size() && s[j] != '/') {
+            if (s[j] == '\\' && j + 1 < s.size()) {
+                if (s[j + 1] != '/') re.push_back('\\');
+                re.push_back(s[j + 1]);
+                j += 2;
+            } else re.push_back(s[j++]);
+        }
+        if (j >= s.size()) return false;  // no closing slash: a plain word
+        ++j;
+        if (j < s.size() && s[j] != ' ' && s[j] != '\t' && s[j] != ')' &&
+            s[j] != '^')
+            return false;
+#ifndef QW_REGEX_QUERY
+        throw std::runtime_error(
+            "query grammar: regex literal /re/ not supported");
+#endif
+        *t = std::move(re);
+        i = j;
+        return true;
+    };
     while (i < s.size()) {
         char c = s[i];
         if (c == ' ' || c == '\t') { ++i; continue; }
@@ -667,6 +728,8 @@ inline std::vector<QTok> qlex(const std::string& s) {
             t.quoted = true;
             t.prefix = after_quote_star();
             if (!t.prefix) t.slop = after_quote_slop();
+        } else if (c == '/' && read_regex(&t.text)) {
+            t.regex = true;
         } else {
             bool esc = false;
             while (i < s.size() && s[i] != ' ' && s[i] != '\t' && s[i] != '(' &&
@@ -687,6 +750,8 @@ inline std::vector<QTok> qlex(const std::string& s) {
                     t.quoted = true;
                     t.prefix = after_quote_star();
                     if (!t.prefix) t.slop = after_quote_slop();
+                } else if (i < s.size() && s[i] == '/' && read_regex(&t.text)) {
+                    t.regex = true;
                 } else if (i < s.size() && (s[i] == '[' || s[i] == '{')) {
                     t.bracket = true;
                     t.lo_incl = s[i] == '[';
@@ -877,6 +942,25 @@ inline PlanNode qtok_leaf_impl(const QTok& t, const std::vector<std::string>& df
         dfs_in.empty() ? schema.default_search_fields : dfs_in;
     PlanNode n;
     bool is_range = t.bracket || t.range_ge || t.range_gt || t.range_le || t.range_lt;
+#ifdef QW_REGEX_QUERY
+    if (t.regex) {
+        // UserInputLeaf::Regex (user_input_query.rs:176-190): the literal's
+        // field, else the single default field
+        std::string field = t.field;
+        if (field.empty()) {
+            if (dfs.empty())
+                throw std::runtime_error(
+                    "regex query without field is not supported");
+            if (dfs.size() > 1)
+                throw std::runtime_error(
+                    "regex query with multiple fields is not supported");
+            field = dfs[0];
+        }
+        n = regex_plan(field, t.text, schema);
+        n.boost = t.boost;
+        return n;
+    }
+#endif
     if (t.field.empty() && !t.quoted && t.text == "*") {
         n.kind = PlanNode::MATCH_ALL;
         return n;
@@ -1267,6 +1351,10 @@ inline PlanNode build_plan(const mj::Value* ast, const Schema& schema) {
 #ifdef QW_PHRASE_WINDOW
     } else if (ty == "phrase_prefix") {
         return phrase_prefix_plan(ast, schema);
+#endif
+#ifdef QW_REGEX_QUERY
+    } else if (ty == "regex") {
+        return regex_plan(ast->at("field")->s, ast->at("regex")->s, schema);
 #endif
     } else if (ty == "user_input") {
         std::vector<std::string> dfs;

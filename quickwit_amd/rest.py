@@ -237,6 +237,17 @@ def es_query_to_ast(q, schema=None, lenient=False):
         if isinstance(body, dict) and body.get("case_insensitive"):
             node["case_insensitive"] = True
         return node
+    if "regexp" in q:
+        # elastic_query_dsl/regex_query.rs: shorthand {"field": "re"} or full
+        # {"field": {"value": "re", "case_insensitive": bool}}
+        [(field, body)] = q["regexp"].items()
+        if isinstance(body, dict):
+            pattern = str(body["value"])
+            if body.get("case_insensitive"):
+                pattern = "(?i)" + pattern
+        else:
+            pattern = str(body)
+        return {"type": "regex", "field": field, "regex": pattern}
     if "bool" in q:
         out = {"type": "bool"}
         for clause in ("must", "must_not", "should", "filter"):
