@@ -213,7 +213,13 @@ struct QueryDev {
     // every match. The running global bound is the u64 at
     // cand_count_off + TOPK_BOUND_OFF, zeroed with the rest of the header.
     uint32_t prune_k;
-    uint32_t _pad_prune;
+    // gated BM25 terms (scored nested booleans): scratch byte
+    // offset of u64 gate[n_terms], each the absolute device VA of a
+    // tile-major u32 bitmap (PRED_BITSET layout) or 0 = ungated term. A
+    // posting scores only where its doc's gate bit is set. 0 = no gates:
+    // the launch runs the ungated instantiations, which never read this
+    // field (it stands where padding stood, so their layout is unchanged).
+    uint32_t gates_off;
 };
 
 // the 64-byte cand_count header at results + cand_count_off: three u32

@@ -145,12 +145,16 @@ struct SmemMap {
 
 // decode every block of `t` overlapping the tile; accumulate into score[] /
 // set bits in `bitset`. SCORE: add BM25 weight (or +1 count) into score.
-template <bool SCORE>
+// GATED (scoring only): `gate` is the term's gate bitmap (tile-major u32
+// words, i.e. bit d of the whole array is doc d) or null; a posting adds
+// its score only where the gate bit of its doc is set.
+template <bool SCORE, bool GATED = false>
 __device__ void decode_term_tile(const QueryDev& q, const TermDev& t, uint32_t tile,
                                  uint32_t tile_lo, uint32_t tile_hi, float* score,
                                  uint32_t* bitset, bool scoring,
                                  const float* ktab_lds = nullptr,
-                                 const uint8_t* norms_lds = nullptr) {
+                                 const uint8_t* norms_lds = nullptr,
+                                 const uint32_t* gate = nullptr) {
     const uint32_t* ranges = (const uint32_t*)t.ranges_addr;
     uint32_t blo = ranges[tile], bhi = ranges[q.n_tiles + tile];
     if (blo >= bhi) return;
@@ -304,7 +308,29 @@ __device__ void decode_term_tile(const QueryDev& q, const TermDev& t, uint32_t t
             s2 = t.weight * (float(tf2) / (float(tf2) + K2));
             s3 = t.weight * (float(tf3) / (float(tf3) + K3));
         }
-        if (SCORE) {
+        if (SCORE && GATED) {
+            // the range guard comes first: boundary blocks and the unused
+            // slots of a short block decode docs outside the tile (any u32),
+            // so only in-tile docs index the gate — those words lie inside
+            // this tile's TILE_DOCS/32 words of the bitmap, the partial last
+            // tile's included. Every other slot reads the tile's first word
+            // and drops the value, which keeps the four loads unconditional.
+            bool in[4];
+            uint32_t gw[4];
+            #pragma unroll
+            for (int el = 0; el < 4; ++el) {
+                uint32_t doc = el == 0 ? doc0 : el == 1 ? doc1 : el == 2 ? doc2 : doc3;
+                in[el] = j0 + el < e.count && doc >= tile_lo && doc < tile_hi;
+                gw[el] = gate ? gate[(in[el] ? doc : tile_lo) >> 5] : 0xFFFFFFFFu;
+            }
+            #pragma unroll
+            for (int el = 0; el < 4; ++el) {
+                uint32_t doc = el == 0 ? doc0 : el == 1 ? doc1 : el == 2 ? doc2 : doc3;
+                float s = el == 0 ? s0 : el == 1 ? s1 : el == 2 ? s2 : s3;
+                if (in[el] && ((gw[el] >> (doc & 31u)) & 1u))
+                    atomicAdd(&score[doc - tile_lo], s);
+            }
+        } else if (SCORE) {
             #pragma unroll
             for (int el = 0; el < 4; ++el) {
                 uint32_t doc = el == 0 ? doc0 : el == 1 ? doc1 : el == 2 ? doc2 : doc3;
@@ -565,8 +591,10 @@ __device__ __forceinline__ void hash_count_add(unsigned long long* tab,
 
 // ---------------------------------------------------------------- main kernel
 // One instantiation per query shape; LDS sections per SmemMap. do_aggs /
-// collect of the old interface became NA / NC.
-template <bool NS, bool NB, bool NA, bool NC, bool PR = false>
+// collect of the old interface became NA / NC. GATED: the should terms
+// score through their gate bitmaps (q.gates_off); launched for scored tree
+// plans only, which have no must / must_not terms (NS && !NB).
+template <bool NS, bool NB, bool NA, bool NC, bool PR = false, bool GATED = false>
 __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
                                                               uint32_t tile_base,
                                                               uint32_t tile_end,
@@ -682,10 +710,19 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
         // ---- should terms: score / count union
         if (NS)
             for (uint32_t t = 0; t < q.n_terms; ++t)
-                if (terms[t].role == ROLE_SHOULD)
-                    decode_term_tile<true>(q, terms[t], tile, tile_lo, tile_hi,
-                                           sc_score, nullptr, q.scoring,
-                                           sc_ktabs, sc_norms);
+                if (terms[t].role == ROLE_SHOULD) {
+                    if constexpr (GATED) {
+                        const uint64_t* gates =
+                            (const uint64_t*)(q.scratch + q.gates_off);
+                        decode_term_tile<true, true>(
+                            q, terms[t], tile, tile_lo, tile_hi, sc_score,
+                            nullptr, q.scoring, sc_ktabs, sc_norms,
+                            (const uint32_t*)gates[t]);
+                    } else
+                        decode_term_tile<true>(q, terms[t], tile, tile_lo, tile_hi,
+                                               sc_score, nullptr, q.scoring,
+                                               sc_ktabs, sc_norms);
+                }
         __syncthreads();
 
         // ---- must groups: union the group's terms into a temp bitset,
@@ -761,7 +798,8 @@ __global__ void __launch_bounds__(TILE_THREADS) k_leaf_tile_t(QueryDev q,
             float sc = 0.f;
             if (NS && have_should) {
                 // shoulds required: scoring path assumes msm==1 and all
-                // weights > 0 (host rejects anything else — product.cpp)
+                // weights > 0 (product.cpp sends anything else elsewhere:
+                // scored_tree_plan, or a refusal)
                 if (q.scoring) {
                     sc = sc_score[li];
                     m = sc > 0.f;
@@ -1192,6 +1230,32 @@ inline uint32_t launch_leaf_tile(bool ns, bool nb, bool na, bool nc, dim3 grid,
     const bool pr = q.prune_k != 0;
     if (pr && (!nc || q.wide_cand || q.prune_k > TOPK_PRUNE_MAX_K))
         throw std::runtime_error("prune_k needs narrow candidate collection");
+    // gated BM25 terms (q.gates_off): four shapes of their own, pruned or
+    // not, so every ungated launch runs the code it ran before gates existed
+    if (q.gates_off) {
+        if (!ns || nb || !q.scoring)
+            throw std::runtime_error("gated terms need a scored should-only plan");
+        #define QW_GATED(NA_, NC_)                                                \
+            if (na == NA_ && nc == NC_) {                                         \
+                const uint32_t lds = SmemMap<true, false, NA_, NC_>::total + stage; \
+                if (NC_ && pr)                                                    \
+                    hipLaunchKernelGGL(                                           \
+                        (k_leaf_tile_t<true, false, NA_, NC_, NC_, true>), grid,  \
+                        dim3(TILE_THREADS), lds, stream, q, tile_base, tile_end,  \
+                        do_count);                                                \
+                else                                                              \
+                    hipLaunchKernelGGL(                                           \
+                        (k_leaf_tile_t<true, false, NA_, NC_, false, true>),      \
+                        grid, dim3(TILE_THREADS), lds, stream, q, tile_base,      \
+                        tile_end, do_count);                                      \
+                return lds;                                                       \
+            }
+        QW_GATED(false, false)
+        QW_GATED(false, true)
+        QW_GATED(true, false)
+        QW_GATED(true, true)
+        #undef QW_GATED
+    }
     #define QW_CASE(NS_, NB_, NA_, NC_)                                           \
         if (ns == NS_ && nb == NB_ && na == NA_ && nc == NC_) {                   \
             const uint32_t lds = SmemMap<NS_, NB_, NA_, NC_>::total + stage;      \

@@ -446,10 +446,21 @@ namespace qw {
 
 // ------------------------------------------------------------ flattening
 // The kernel executes ONE flattened boolean level (should/must/must_not term
-// lists + fast-field predicates). Nested plans that cannot be flattened are
-// rejected with InvalidQuery — never silently mis-answered. This covers every
-// BASELINE.json config and the golden-suite query shapes (term, full_text
-// and/or, bool with term/range clauses, range, match_all).
+// lists + fast-field predicates). This covers every BASELINE.json config and
+// the golden-suite query shapes (term, full_text and/or, bool with
+// term/range clauses, range, match_all). A plan that does not flatten throws
+// NotFlattenable and is answered from device bitmaps instead
+// (flatten_or_bitmap): unscored, the whole tree becomes one PRED_BITSET;
+// scored, scored_tree_plan turns its term leaves into gated should terms
+// (DESIGN.md §7a). What neither route computes exactly is refused with
+// InvalidQuery — never silently mis-answered.
+struct NotFlattenable : std::runtime_error {
+    // TREE: a boolean shape; with or without scores the bitmap routes answer
+    // it. BITMAP: phrase / regex, which have a match set but no score.
+    enum Why { TREE, BITMAP } why;
+    NotFlattenable(Why w, const char* msg) : std::runtime_error(msg), why(w) {}
+};
+
 struct FlatQuery {
     bool match_none = false;
     bool match_all = false;  // positive base = all docs (preds still filter)
@@ -473,6 +484,9 @@ struct FlatQuery {
     std::vector<const PlanNode*> cache_nodes;
     std::vector<PredDev> preds;
     std::vector<const TextFieldView*> ktab_fields;  // ktab_idx -> field
+    // scored tree plans: per term, the device VA of its gate bitmap (0 =
+    // ungated term). Empty = no term is gated, the plain tile kernel runs.
+    std::vector<uint64_t> gates;
 
     uint32_t ktab_for(const TextFieldView* f) {
         for (size_t i = 0; i < ktab_fields.size(); ++i)
@@ -691,15 +705,18 @@ static void add_positive(FlatQuery& fq, const SplitView& sv, const PlanNode& c,
                              boost * c.boost * s.boost, scored, grp, true);
                 if (fq.terms.size() == before) fq.match_none = true;
             } else {
-                throw std::runtime_error(
+                throw NotFlattenable(
+                    NotFlattenable::TREE,
                     "nested boolean inside must/filter not flattenable (GPU r1)");
             }
             break;
         case PlanNode::PHRASE:
-            throw std::runtime_error(
+            throw NotFlattenable(
+                NotFlattenable::BITMAP,
                 "phrase clause not flattenable (device-bitmap path)");
         case PlanNode::REGEX:
-            throw std::runtime_error(
+            throw NotFlattenable(
+                NotFlattenable::BITMAP,
                 "regex clause not flattenable (device-bitmap path)");
     }
 }
@@ -738,7 +755,8 @@ static void flatten_bool(FlatQuery& fq, const SplitView& sv, const PlanNode& n,
         } else if (c.kind == PlanNode::MATCH_NONE) {
             // contributes nothing
         } else {
-            throw std::runtime_error("should clause not flattenable (GPU r1)");
+            throw NotFlattenable(NotFlattenable::TREE,
+                                 "should clause not flattenable (GPU r1)");
         }
     }
 
@@ -758,7 +776,8 @@ static void flatten_bool(FlatQuery& fq, const SplitView& sv, const PlanNode& n,
         } else if (c.kind == PlanNode::MATCH_ALL) {
             fq.match_none = true;
         } else
-            throw std::runtime_error("must_not clause not flattenable (GPU r1)");
+            throw NotFlattenable(NotFlattenable::TREE,
+                                 "must_not clause not flattenable (GPU r1)");
     }
 
     int64_t msm = n.minimum_should_match;
@@ -795,10 +814,16 @@ static void flatten_bool(FlatQuery& fq, const SplitView& sv, const PlanNode& n,
         fq.match_none = true;  // required shoulds but every term absent
         return;
     }
+    // the tile kernel's scored match test is "score > 0", which is msm == 1
+    // over the shoulds alone; scored_tree_plan answers the other two forms
     if (fq.scoring && msm > 0 && n_must_terms > 0)
-        throw std::runtime_error("scored msm>0 with must terms not supported (GPU r1)");
+        throw NotFlattenable(
+            NotFlattenable::TREE,
+            "scored msm>0 with must terms not supported (GPU r1)");
     if (fq.scoring && msm > 1)
-        throw std::runtime_error("scored minimum_should_match>1 not supported (GPU r1)");
+        throw NotFlattenable(
+            NotFlattenable::TREE,
+            "scored minimum_should_match>1 not supported (GPU r1)");
     // base: match_all when no must terms (pred-only/should-optional base)
     fq.match_all = n_must_terms == 0 && (has_req || msm == 0);
     if (!has_req && msm == 0 && n.should.empty()) fq.match_none = true;
@@ -812,11 +837,11 @@ static FlatQuery flatten(const SplitView& sv, const PlanNode& plan, bool scoring
             "term_set/wildcard/phrase/regex under _score sorting not supported "
             "(const-score semantics, qast.h)");
     if (plan.kind == PlanNode::PHRASE)
-        throw std::runtime_error(
-            "phrase not flattenable (device-bitmap path)");
+        throw NotFlattenable(NotFlattenable::BITMAP,
+                             "phrase not flattenable (device-bitmap path)");
     if (plan.kind == PlanNode::REGEX)
-        throw std::runtime_error(
-            "regex not flattenable (device-bitmap path)");
+        throw NotFlattenable(NotFlattenable::BITMAP,
+                             "regex not flattenable (device-bitmap path)");
     switch (plan.kind) {
         case PlanNode::MATCH_ALL:
             fq.match_all = true;
@@ -1983,16 +2008,118 @@ static SortPlan make_sort_plan(const SplitView& sv, const pb::SearchRequest& req
     return sp;
 }
 
+// the combined gate bitmaps of one split search (AND of two or more node
+// bitmaps; the node bitmaps themselves belong to the hitset cache). Counted
+// in hbm_used while they live, freed when the search ends, by whatever exit.
+struct GateBitmaps {
+    qw_ctx* ctx;
+    std::vector<std::pair<uint8_t*, size_t>> bms;
+    explicit GateBitmaps(qw_ctx* c) : ctx(c) {}
+    GateBitmaps(const GateBitmaps&) = delete;
+    GateBitmaps& operator=(const GateBitmaps&) = delete;
+    ~GateBitmaps() {
+        for (auto& b : bms) {
+            (void)hipFree(b.first);  // waits for the kernels reading it
+            ctx->hbm_used -= b.second;
+        }
+    }
+    uint8_t* alloc(size_t bytes) {
+        qw_check_budget(ctx, bytes);
+        uint8_t* p = nullptr;
+        HIP_CHECK(hipMalloc(&p, bytes));
+        bms.emplace_back(p, bytes);
+        ctx->hbm_used += bytes;
+        return p;
+    }
+};
+
+// Scored plan that does not flatten. The oracle's eval_bool
+// scores a bool as boost * (sum of its matching must and should children),
+// so a term leaf t adds W_t * tfnorm(t, d) iff d is in t's postings and every
+// bool between t and the root matches d; W_t carries every boost on the path.
+// The plan is match_all + PRED_BITSET(root match set) with every such leaf as
+// an optional should term (msm 0) whose score is gated by the AND of those
+// ancestors' match sets. Three facts shrink a gate:
+//   - the root is the PRED_BITSET, which drops non-matching docs anyway;
+//   - a bool reached over a must edge matches wherever its parent does;
+//   - a pure OR of terms matches wherever one of its terms does.
+// What is left is the bools reached over a should edge: none for most
+// leaves, one memoized node bitmap for many, a combined temporary otherwise.
+struct ScoredTreePlanner {
+    qw_ctx* ctx;
+    const DeviceSplit& ds;
+    const Schema& schema;
+    GateBitmaps& tmp;
+    FlatQuery& fq;
+    size_t bm_bytes;
+    bool any_gate = false;
+
+    void walk(const PlanNode& raw, float boost, const uint8_t* gate) {
+        const PlanNode& n = uncache(raw);
+        if (n.kind == PlanNode::TERM) {
+            size_t before = fq.terms.size();
+            add_term(fq, ds.view, n.field, n.value, ROLE_SHOULD, boost * n.boost,
+                     true);
+            if (fq.terms.size() == before) return;  // not in the dictionary
+            if (fq.terms.back().weight <= 0.f)
+                throw std::runtime_error("non-positive BM25 weight (boost<=0?)");
+            fq.gates.push_back((uint64_t)gate);
+            any_gate |= gate != nullptr;
+            return;
+        }
+        if (n.kind != PlanNode::BOOL) return;  // matches, never scores
+        boost *= n.boost;
+        for (const PlanNode& c : n.must) walk(c, boost, gate);
+        for (const PlanNode& c_raw : n.should) {
+            const PlanNode& c = uncache(c_raw);
+            const uint8_t* g = gate;
+            if (c.kind == PlanNode::BOOL && !is_pure_should_terms(c)) {
+                const uint8_t* node_bm = bitmap_eval(ctx, ds, c, schema);
+                if (!gate) {
+                    g = node_bm;
+                } else {
+                    uint8_t* both = tmp.alloc(bm_bytes);
+                    bitmap_combine(ctx, both, node_bm, bm_bytes, 3u);
+                    bitmap_combine(ctx, both, gate, bm_bytes, 0u);
+                    g = both;
+                }
+            }
+            walk(c, boost, g);
+        }
+    }
+};
+
+static FlatQuery scored_tree_plan(qw_ctx* ctx, const DeviceSplit& ds,
+                                  const PlanNode& plan, const Schema& schema,
+                                  GateBitmaps& tmp) {
+    FlatQuery fq;
+    fq.scoring = true;
+    fq.match_all = true;
+    fq.msm = 0;  // the shoulds only add score; the bitmap decides the match
+    PredDev p{};
+    p.type = PRED_BITSET;
+    p.abs_bitmap = (uint64_t)bitmap_eval(ctx, ds, plan, schema);
+    fq.preds.push_back(p);
+    uint32_t n_tiles = (ds.view.num_docs + TILE_DOCS - 1) / TILE_DOCS;
+    ScoredTreePlanner pl{ctx, ds, schema, tmp, fq,
+                         size_t(n_tiles) * (TILE_DOCS / 32) * 4};
+    pl.walk(plan, 1.f, nullptr);
+    if (!pl.any_gate) fq.gates.clear();
+    return fq;
+}
+
 // plan -> FlatQuery, with every bitmap-backed predicate resolved
 static FlatQuery flatten_or_bitmap(qw_ctx* ctx, const DeviceSplit& ds,
                                    const PlanNode& plan, const Schema& schema,
-                                   bool scoring) {
+                                   bool scoring, GateBitmaps& gate_tmp) {
     FlatQuery fq;
     try {
         fq = flatten(ds.view, plan, scoring);
-    } catch (const std::exception& e) {
-        std::string msg = e.what();
-        if (scoring || msg.find("flatten") == std::string::npos) throw;
+    } catch (const NotFlattenable& e) {
+        if (scoring) {
+            if (e.why != NotFlattenable::TREE) throw;
+            return scored_tree_plan(ctx, ds, plan, schema, gate_tmp);
+        }
         // unscored plan the single-pass kernel cannot express: evaluate the
         // whole boolean recursively into a device bitmap and search
         // match_all + PRED_BITSET (results identical; scores don't exist)
@@ -2093,8 +2220,9 @@ static TermTables build_term_tables(const SplitView& sv, FlatQuery& fq) {
 // byte offsets of one query's two device regions
 struct ScratchLayout {
     // query scratch (one H2D): TermDev[] | PredDev[] | AggDev[] | K tables |
-    // percentiles boundary tables
+    // percentiles boundary tables | term gates (scored tree plans)
     size_t off_terms = 0, off_preds = 0, off_aggs = 0, off_ktabs = 0;
+    size_t off_gates = 0;  // 0 = no gated term
     size_t scratch_bytes = 0;
     // results: tile counts | 64 B cand_count header (gpu_types.h) | selection
     // histogram | aggregation output | candidate records
@@ -2138,6 +2266,10 @@ static void layout_finish(ScratchLayout& L, const TermTables& tt,
             ap.devs[i].p_bound_off = L.scratch_bytes;
             L.scratch_bytes += ap.pbounds[i].size() * 8;
         }
+    if (!fq.gates.empty()) {
+        L.off_gates = L.scratch_bytes;  // 8-aligned, past the K tables: never 0
+        L.scratch_bytes += fq.gates.size() * 8;
+    }
 }
 
 // dense positive base => eager predicate evaluation (kernels.hip):
@@ -2179,6 +2311,8 @@ static void assemble_scratch(uint8_t* scratch, const ScratchLayout& L,
         if (!ap.pbounds[i].empty())
             memcpy(scratch + ap.devs[i].p_bound_off, ap.pbounds[i].data(),
                    ap.pbounds[i].size() * 8);
+    if (L.off_gates)
+        memcpy(scratch + L.off_gates, fq.gates.data(), fq.gates.size() * 8);
 }
 
 // everything launch_leaf_tile needs for one query
@@ -2285,9 +2419,13 @@ static TileLaunch fill_query_dev(qw_ctx* ctx, const DeviceSplit& ds,
         leaf_max_hits <= TOPK_PRUNE_MAX_K && ctx->topk_prune)
         q.prune_k = uint32_t(leaf_max_hits);
 
-    tl.kname = !fq.terms.empty() ? "union_bm25"
-               : do_aggs         ? "column_agg"
-                                 : "range_filter";
+    // gated should terms: pruning stays on, its bound comes from the final
+    // keys of matched docs, whatever summed into their scores
+    q.gates_off = uint32_t(L.off_gates);
+    tl.kname = L.off_gates         ? "union_bm25_gated"
+               : !fq.terms.empty() ? "union_bm25"
+               : do_aggs           ? "column_agg"
+                                   : "range_filter";
     uint32_t n_should = uint32_t(tt.terms.size()) - tt.n_must - tt.n_must_not;
     tl.ns = n_should > 0 || (fq.scoring && !tt.terms.empty());
     tl.nb = tt.n_must > 0 || tt.n_must_not > 0;
@@ -2891,7 +3029,8 @@ static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
 
     PlanNode plan = leaf_plan(ctx, sv, req, schema);
     SortPlan sp = make_sort_plan(sv, req);
-    FlatQuery fq = flatten_or_bitmap(ctx, ds, plan, schema, sp.scoring);
+    GateBitmaps gate_tmp(ctx);  // outlives every launch below
+    FlatQuery fq = flatten_or_bitmap(ctx, ds, plan, schema, sp.scoring, gate_tmp);
     // report required terms flattening proved absent; the caller inserts
     // into the absence cache (for multi-segment splits only terms absent
     // from EVERY segment qualify)
