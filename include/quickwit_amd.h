@@ -183,6 +183,16 @@ int32_t qw_absence_cache_stats(qw_ctx* ctx, uint64_t* hits, uint64_t* misses,
  * collecting call. With pruning off the two are equal. */
 int32_t qw_topk_stats(qw_ctx* ctx, uint64_t out[4]);
 
+/* One-sync top-K selection counters. A collecting leaf-split call without a
+ * search_after cursor lets the device pick the K-boundary bin and compact
+ * the survivors behind the tile kernel, so that they arrive with the call's
+ * one synchronize (config "topk_onesync": false keeps the host-side pick).
+ * out[0] = calls served that way, out[1] = calls whose boundary bin held too
+ * many records and fell back to the host refinement loop, out[2] = survivor
+ * records of the last one-sync call, out[3] = 1 when that call needed a
+ * second copy for survivors beyond the inline ones, else 0. */
+int32_t qw_topk_onesync_stats(qw_ctx* ctx, uint64_t out[4]);
+
 /* Library version + build arch, e.g. "quickwit_amd 0.1 gfx950". */
 const char* qw_version(void);
 

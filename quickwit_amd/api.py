@@ -210,6 +210,20 @@ class GpuSearcher(_BaseSearcher):
             raise RuntimeError(f"topk_stats failed: {rc}")
         return tuple(out)
 
+    def topk_onesync_stats(self):
+        """(onesync_calls, fallback_calls, last_survivors, last_tail_copy):
+        collecting leaf-split calls whose survivors came with the call's one
+        synchronize / that fell back to the host refinement loop, the last
+        one-sync call's survivor records, and 1 when it needed the second
+        copy. Config {"topk_onesync": False} keeps the host-side pick."""
+        fn = self._lib.qw_topk_onesync_stats
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64 * 4)]
+        out = (ctypes.c_uint64 * 4)()
+        rc = fn(self._ctx, ctypes.byref(out))
+        if rc != 0:
+            raise RuntimeError(f"topk_onesync_stats failed: {rc}")
+        return tuple(out)
+
     def device_sync(self):
         self._lib.qw_ctx_device_sync.argtypes = [ctypes.c_void_p]
         rc = self._lib.qw_ctx_device_sync(self._ctx)

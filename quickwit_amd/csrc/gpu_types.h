@@ -223,9 +223,22 @@ struct QueryDev {
 };
 
 // the 64-byte cand_count header at results + cand_count_off: three u32
-// counters, then the pruning bound (u64) at byte TOPK_BOUND_OFF
+// counters, then the pruning bound (u64) at byte TOPK_BOUND_OFF, then what
+// the device-side pick of the one-sync selection leaves for the host
+// (k_cand_pick_compact, kernels.hip): the survivor count it read off the
+// pass-0 histogram (u32 at TOPK_PICK_COUNT_OFF), the "needs refinement" flag
+// (u32 at TOPK_PICK_REFINE_OFF) and the floor key it compacted by (u64 at
+// TOPK_PICK_FLOOR_OFF). All zeroed with the rest of the header.
 constexpr uint32_t TOPK_BOUND_OFF = 16;
+constexpr uint32_t TOPK_PICK_COUNT_OFF = 24;
+constexpr uint32_t TOPK_PICK_REFINE_OFF = 28;
+constexpr uint32_t TOPK_PICK_FLOOR_OFF = 32;
 constexpr uint32_t TOPK_PRUNE_MAX_K = 64;
+// selection refines until at most max(4 K, TOPK_REFINE_MIN) records survive
+constexpr uint32_t TOPK_REFINE_MIN = 16384;
+// survivor records that ride the one-sync download; a longer survivor list
+// costs one more copy of its tail
+constexpr uint32_t TOPK_INLINE_SURVIVORS = 4096;
 inline uint32_t* cand_hdr_candidates(uint8_t* hdr) { return (uint32_t*)hdr; }
 inline uint32_t* cand_hdr_survivors(uint8_t* hdr) { return (uint32_t*)hdr + 1; }
 // candidates left inside the search_after cursor band

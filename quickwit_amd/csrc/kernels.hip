@@ -1378,6 +1378,125 @@ __device__ __forceinline__ void cand_compact_body(uint32_t bdim,
     }
 }
 
+// what the first iteration of TopkSelector::select's host loop decides, from
+// the finished pass-0 histogram of all n candidates
+struct TopkPick {
+    uint64_t floor_key;  // survivors are the records with key >= floor_key
+    uint32_t survivors;
+    uint32_t refine;     // 1 = more than T records share the boundary bin: the
+                         // host refines, nothing is compacted
+};
+constexpr uint32_t TOPK_PICK_THREADS = 256;
+constexpr uint32_t TOPK_PICK_BINS = TOPK_BINS / TOPK_PICK_THREADS;  // per thread
+static_assert(TOPK_PICK_BINS == 16, "topk_pick loads its bins as four uint4");
+
+// Every thread of a TOPK_PICK_THREADS-wide workgroup returns the same pick.
+// Thread t owns the 16 bins below 4095 - 16 t; an inclusive scan of the
+// per-thread sums, top bin first, finds the one thread whose bins cross K,
+// and that thread walks its bins exactly as the host walks all 4096.
+__device__ __forceinline__ TopkPick topk_pick(const uint32_t* hist, uint32_t n,
+                                              uint32_t kwant) {
+    TopkPick p;
+    const uint32_t K = kwant < n ? kwant : n;
+    const uint64_t k4 = 4ull * K;
+    const uint64_t T = k4 > TOPK_REFINE_MIN ? k4 : TOPK_REFINE_MIN;
+    p.floor_key = 0;
+    p.survivors = n;
+    p.refine = 0;
+    if (n <= T) return p;  // n is uniform: no thread reaches the barriers below
+
+    __shared__ uint32_t scan[TOPK_PICK_THREADS];
+    __shared__ uint32_t found[3];  // boundary bin, records above it, its count
+    const uint32_t t = threadIdx.x;
+    const uint32_t lo = TOPK_BINS - TOPK_PICK_BINS * (t + 1);  // lowest own bin
+    uint32_t h[TOPK_PICK_BINS];
+    const uint4* src = (const uint4*)(hist + lo);
+#pragma unroll
+    for (uint32_t j = 0; j < TOPK_PICK_BINS / 4; ++j) {
+        uint4 v = src[j];
+        h[4 * j] = v.x;
+        h[4 * j + 1] = v.y;
+        h[4 * j + 2] = v.z;
+        h[4 * j + 3] = v.w;
+    }
+    uint32_t own = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < TOPK_PICK_BINS; ++j) own += h[j];
+    scan[t] = own;
+    if (t == 0) found[0] = 0xFFFFFFFFu;
+    __syncthreads();
+    for (uint32_t off = 1; off < TOPK_PICK_THREADS; off <<= 1) {
+        uint32_t v = t >= off ? scan[t - off] : 0;
+        __syncthreads();
+        scan[t] += v;
+        __syncthreads();
+    }
+    // the bins hold n <= 2^32 - 1 records in all: no sum here can wrap
+    const uint32_t incl = scan[t], excl = incl - own;
+    if (excl < K && incl >= K) {  // exactly one thread
+        uint32_t cum = excl, b = 0, hb = 0;
+        bool done = false;
+#pragma unroll
+        for (int j = int(TOPK_PICK_BINS) - 1; j >= 0; --j) {
+            if (done) continue;
+            if (cum + h[j] >= K) {
+                done = true;
+                b = lo + uint32_t(j);
+                hb = h[j];
+            } else cum += h[j];
+        }
+        found[0] = b;
+        found[1] = cum;
+        found[2] = hb;
+    }
+    __syncthreads();
+    if (found[0] == 0xFFFFFFFFu) {
+        // the bins sum to less than K <= n: pass 0 did not count every
+        // record. Not reachable; the host loop decides.
+        p.refine = 1;
+        return p;
+    }
+    p.floor_key = uint64_t(found[0]) << (64 - 12);
+    p.survivors = found[1] + found[2];
+    p.refine = p.survivors > T ? 1 : 0;
+    return p;
+}
+
+// One-sync selection: the pick, then the compaction by its floor key, in one
+// launch behind pass 0. Each workgroup recomputes the pick from the 16 KB
+// global histogram (no hand-off between workgroups); workgroup 0 alone
+// leaves it in the header for the host. `hdr` is the cand_count header as
+// u32 words, `cand_cap` the candidate array's capacity (bounds the count
+// read here), `cap` the capacity of `out` in records.
+template <uint32_t RW>
+__device__ __forceinline__ void cand_pick_compact_body(
+    uint32_t bdim, const uint64_t* cand, uint32_t cand_cap, uint32_t* hdr,
+    const uint32_t* hist, uint32_t kwant, uint64_t* out, uint32_t cap) {
+    uint32_t n = hdr[0];
+    if (n > cand_cap) n = cand_cap;
+    TopkPick p = topk_pick(hist, n, kwant);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        hdr[TOPK_PICK_COUNT_OFF / 4] = p.survivors;
+        hdr[TOPK_PICK_REFINE_OFF / 4] = p.refine;
+        *(uint64_t*)(hdr + TOPK_PICK_FLOOR_OFF / 4) = p.floor_key;
+    }
+    if (p.refine) return;
+    cand_compact_body<RW>(bdim, cand, n, p.floor_key, ~0ull, out, hdr + 1, cap);
+}
+
+extern "C" __global__ void __launch_bounds__(TOPK_PICK_THREADS)
+k_cand_pick_compact(const uint64_t* cand, uint32_t cand_cap, uint32_t* hdr,
+                    const uint32_t* hist, uint32_t kwant, uint64_t* out,
+                    uint32_t cap) {
+    cand_pick_compact_body<1>(blockDim.x, cand, cand_cap, hdr, hist, kwant, out, cap);
+}
+extern "C" __global__ void __launch_bounds__(TOPK_PICK_THREADS)
+k_cand_pick_compact_w(const uint64_t* cand, uint32_t cand_cap, uint32_t* hdr,
+                      const uint32_t* hist, uint32_t kwant, uint64_t* out,
+                      uint32_t cap) {
+    cand_pick_compact_body<2>(blockDim.x, cand, cand_cap, hdr, hist, kwant, out, cap);
+}
+
 extern "C" __global__ void k_cand_hist(const uint64_t* cand, const uint32_t* n_ptr,
                                        uint64_t prefix, uint32_t prefix_bits,
                                        uint32_t* hist) {

@@ -360,6 +360,15 @@ struct qw_ctx {
     bool topk_prune = true;
     uint64_t topk_pruned = 0, topk_unpruned = 0;
     uint64_t topk_last_emitted = 0, topk_last_matched = 0;
+    // one-sync top-K selection (TopkSelector); config key "topk_onesync"
+    // (bool, default true) turns it off for this context. Counters for
+    // qw_topk_onesync_stats: collecting calls whose survivors came with the
+    // main synchronize / that fell back to the host refinement loop, and
+    // the last one-sync call's survivor count and whether it needed the
+    // second copy.
+    bool topk_onesync = true;
+    uint64_t topk_onesync_calls = 0, topk_onesync_fallbacks = 0;
+    uint64_t topk_onesync_last_survivors = 0, topk_onesync_last_tail = 0;
 };
 
 static void qw_check_budget(qw_ctx* ctx, uint64_t need) {
@@ -2493,6 +2502,19 @@ static void launch_cand_compact(bool wide, uint32_t grid, hipStream_t stream,
         hipLaunchKernelGGL(k_cand_compact, dim3(grid), dim3(256), 0, stream, cand,
                            n, floor_key, ceil_key, out, out_count, cap);
 }
+static void launch_cand_pick_compact(bool wide, uint32_t grid, hipStream_t stream,
+                                     const uint64_t* cand, uint32_t cand_cap,
+                                     uint32_t* hdr, const uint32_t* hist,
+                                     uint32_t kwant, uint64_t* out, uint32_t cap) {
+    if (wide)
+        hipLaunchKernelGGL(k_cand_pick_compact_w, dim3(grid),
+                           dim3(TOPK_PICK_THREADS), 0, stream, cand, cand_cap, hdr,
+                           hist, kwant, out, cap);
+    else
+        hipLaunchKernelGGL(k_cand_pick_compact, dim3(grid),
+                           dim3(TOPK_PICK_THREADS), 0, stream, cand, cand_cap, hdr,
+                           hist, kwant, out, cap);
+}
 
 // inclusive upper bound, in device-key space, of the search_after cursor's
 // primary-value band (ties and the (v2, split, seg, doc) chain are settled
@@ -2541,6 +2563,14 @@ struct TopkSelector {
     uint64_t band_n = 0;  // records in d_cand
     uint64_t kwant = 0;   // K of the last select()
     std::vector<uint64_t> top_keys;  // survivors (narrow: sorted best-first)
+    // one-sync selection: the device picked the floor key and compacted
+    // behind pass 0, and the first TOPK_INLINE_SURVIVORS survivor records
+    // came down with the main synchronize
+    uint32_t* d_hdr = nullptr;       // cand_count header as u32 words
+    uint32_t cand_cap = 0;           // candidate array capacity, records
+    uint32_t surv_cap = 0;           // ctx->d_survivors capacity, records
+    bool onesync = false;            // this call enqueued the one-sync batch
+    uint32_t picked_survivors = 0;   // valid while `onesync`
 
     TopkSelector(qw_ctx* c, bool wide_, bool after_, uint64_t leaf_max_hits_)
         : ctx(c), wide(wide_), after(after_), rw(wide_ ? 2 : 1),
@@ -2558,23 +2588,137 @@ struct TopkSelector {
         d_survivors = cand_hdr_survivors(hdr);
         d_band = cand_hdr_cursor_band(hdr);
         d_n = d_candidates;
+        d_hdr = (uint32_t*)hdr;
+        cand_cap = uint32_t(L.cand_cap);
     }
 
     // enqueue histogram pass 0 behind the main kernel (count read
     // device-side) so its result arrives with the same synchronize
     // (kept when pruning: the 100M flagship still emits ~130k records,
     // above the 16384 no-refinement threshold, and a pass over that few
-    // costs far less than the extra round trip select() would need)
-    void enqueue_pass0(uint32_t num_docs) {
-        HIP_CHECK(hipMemsetAsync(d_hist, 0, TOPK_BINS * 4, ctx->stream));
+    // costs far less than the extra round trip select() would need).
+    // `prezeroed`: the histogram still holds the zeros of the results reset
+    // (enqueue_uploads), nothing has written it since.
+    void enqueue_pass0(uint32_t num_docs, bool prezeroed = false) {
+        if (!prezeroed)
+            HIP_CHECK(hipMemsetAsync(d_hist, 0, TOPK_BINS * 4, ctx->stream));
         // candidate count is device-side only at this point: size the
         // grid for the worst case (every doc a candidate)
         uint32_t hgrid = std::min<uint32_t>(512, (num_docs + 4095) / 4096);
         launch_cand_hist(wide, hgrid, ctx->stream, d_cand, d_candidates, 0ull, 0u,
                          d_hist);
+    }
+
+    // the two-sync flow's download of pass 0, into its own staging
+    void download_pass0() {
         HIP_CHECK(hipMemcpyAsync(hist0, d_hist, TOPK_BINS * 4,
                                  hipMemcpyDeviceToHost, ctx->stream));
         hist0_valid = true;
+    }
+
+    // one-sync selection serves collecting calls without a search_after
+    // cursor (the cursor band is cut out of all candidates first)
+    bool onesync_wanted(bool collect) const {
+        return collect && !after && ctx->topk_onesync;
+    }
+
+    // One-sync selection, step 1, before anything is enqueued (growing a
+    // device buffer synchronizes): room for every survivor list the device
+    // pick can leave. It compacts at most T = max(4 K, TOPK_REFINE_MIN)
+    // records, K <= min(leaf_max_hits, num_docs), never more than there are
+    // candidates (<= num_docs), and the inline download reads
+    // TOPK_INLINE_SURVIVORS records whatever the count.
+    void reserve_onesync(uint32_t num_docs) {
+        uint64_t k = std::min<uint64_t>(leaf_max_hits, num_docs);
+        uint64_t t = std::min<uint64_t>(std::max<uint64_t>(4 * k, TOPK_REFINE_MIN),
+                                        num_docs);
+        surv_cap = uint32_t(std::max<uint64_t>(t, TOPK_INLINE_SURVIVORS));
+        qw_ensure_acct(ctx, ctx->d_survivors, size_t(surv_cap) * 8 * rw + 16);
+        ctx->h_topk.ensure(size_t(TOPK_INLINE_SURVIVORS) * 8 * rw);
+    }
+
+    // step 2, behind the tile kernel: pass 0, then the pick and the
+    // compaction in one launch (k_cand_pick_compact), then the inline
+    // survivors. The histogram and the survivor counter still hold the zeros
+    // of the results reset. `few`: the tile kernel pruned, so the candidates
+    // are few and a small grid keeps the per-workgroup pick cheap.
+    void enqueue_onesync(uint32_t num_docs, bool few) {
+        enqueue_pass0(num_docs, true);
+        uint32_t cgrid = few ? 256u
+                             : std::min<uint32_t>(2048, (num_docs + 1023) / 1024);
+        uint32_t kw = uint32_t(std::min<uint64_t>(leaf_max_hits, 0xFFFFFFFFull));
+        launch_cand_pick_compact(wide, cgrid, ctx->stream, d_cand, cand_cap, d_hdr,
+                                 d_hist, kw, (uint64_t*)ctx->d_survivors.p,
+                                 surv_cap);
+        HIP_CHECK(hipMemcpyAsync(ctx->h_topk.p, ctx->d_survivors.p,
+                                 size_t(TOPK_INLINE_SURVIVORS) * 8 * rw,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+        onesync = true;
+    }
+
+    // step 3, after the synchronize: `hdr` and `hist` are the downloaded
+    // header and pass-0 histogram. Returns through `onesync` whether the
+    // survivors are there or select() has to refine from `hist`.
+    void onesync_arrived(const uint8_t* hdr, const uint8_t* hist) {
+        uint32_t refine, compacted;
+        memcpy(&picked_survivors, hdr + TOPK_PICK_COUNT_OFF, 4);
+        memcpy(&refine, hdr + TOPK_PICK_REFINE_OFF, 4);
+        memcpy(&compacted, hdr + 4, 4);  // cand_hdr_survivors
+        hist0 = (uint32_t*)hist;
+        hist0_valid = true;
+        if (refine) {
+            onesync = false;
+            ++ctx->topk_onesync_fallbacks;
+            return;
+        }
+        if (compacted != picked_survivors || picked_survivors > surv_cap)
+            throw std::runtime_error(
+                "top-K one-sync selection: histogram and compaction disagree (" +
+                std::to_string(picked_survivors) + " vs " +
+                std::to_string(compacted) + ")");
+        ++ctx->topk_onesync_calls;
+        ctx->topk_onesync_last_survivors = picked_survivors;
+        ctx->topk_onesync_last_tail = picked_survivors > TOPK_INLINE_SURVIVORS;
+    }
+
+    // step 4: the survivors are in pinned staging, but for a tail beyond the
+    // inline records; the same exact sort as the refinement path
+    void take_onesync(uint64_t K) {
+        const size_t rec = size_t(8) * rw;
+        const size_t n = picked_survivors;
+        const size_t inl = std::min<size_t>(n, TOPK_INLINE_SURVIVORS);
+        top_keys.resize(n * rw);
+        memcpy(top_keys.data(), ctx->h_topk.p, inl * rec);
+        if (n > inl) {
+            ctx->h_topk.ensure((n - inl) * rec);
+            HIP_CHECK(hipEventRecord(ctx->ev_start, ctx->stream));
+            HIP_CHECK(hipMemcpyAsync(ctx->h_topk.p, ctx->d_survivors.p + inl * rec,
+                                     (n - inl) * rec, hipMemcpyDeviceToHost,
+                                     ctx->stream));
+            HIP_CHECK(hipEventRecord(ctx->ev_stop, ctx->stream));
+            HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            memcpy(top_keys.data() + inl * rw, ctx->h_topk.p, (n - inl) * rec);
+            float tms = 0;
+            HIP_CHECK(hipEventElapsedTime(&tms, ctx->ev_start, ctx->ev_stop));
+            record_kernel_time(ctx, "topk_select", tms);
+        }
+        sort_truncate(K);
+    }
+
+    // narrow keys: best first, cut to K unless a cursor filter still has to
+    // run over them. Keys are distinct (the doc id is part of the key), so
+    // sorting only the K best of a longer list gives the same K keys in the
+    // same order as sorting all and cutting (1,323 survivors at the 100M
+    // flagship: the full sort was ~30 us of the call).
+    void sort_truncate(uint64_t K) {
+        if (wide) return;
+        const bool cut = top_keys.size() > K && !after;
+        if (cut && K <= top_keys.size() / 8)  // heap select pays for small K
+            std::partial_sort(top_keys.begin(), top_keys.begin() + K,
+                              top_keys.end(), std::greater<uint64_t>());
+        else
+            std::sort(top_keys.begin(), top_keys.end(), std::greater<uint64_t>());
+        if (cut) top_keys.resize(K);
     }
 
     // search_after: pre-compact the band_n candidates to the cursor's
@@ -2600,6 +2744,11 @@ struct TopkSelector {
         kwant = Kwant;
         const uint32_t cand_n = uint32_t(band_n);
         uint64_t K = std::min<uint64_t>(Kwant, cand_n);
+        if (onesync) {
+            onesync = false;
+            take_onesync(K);
+            return;
+        }
         uint64_t prefix = 0;
         uint32_t prefix_bits = 0;
         uint64_t survivors = cand_n, above = 0, Krem = K;
@@ -2663,10 +2812,7 @@ struct TopkSelector {
         float tms = 0;
         HIP_CHECK(hipEventElapsedTime(&tms, ctx->ev_start, ctx->ev_stop));
         record_kernel_time(ctx, "topk_select", tms);
-        if (!wide) {
-            std::sort(top_keys.begin(), top_keys.end(), std::greater<uint64_t>());
-            if (top_keys.size() > K && !after) top_keys.resize(K);
-        }
+        sort_truncate(K);
     }
 
     // search_after shortfall: the exact cursor filter left fewer than a page
@@ -2684,6 +2830,8 @@ struct TopkSelector {
 struct TileRun {
     uint64_t matched = 0;  // sum of the tile counts
     uint32_t cand_n = 0;   // candidate records written
+    // downloaded aggregation output (pinned staging), when there are aggs
+    const uint8_t* agg_host = nullptr;
 };
 
 // query scratch upload + results reset; enqueued before fill_query_dev so
@@ -2710,28 +2858,51 @@ static TileRun run_leaf_tile(qw_ctx* ctx, const SplitView& sv,
                      tl.q, 0u, n_tiles, 1u);
     HIP_CHECK(hipEventRecord(ctx->ev_stop, ctx->stream));
     HIP_CHECK(hipGetLastError());
-    if (collect && !sel.after) sel.enqueue_pass0(sv.num_docs);
-
-    // ---- download counts (into pinned staging: no pageable D2H)
-    ctx->h_counts.ensure(size_t(n_tiles) * 4 + 64);
-    uint32_t* tile_counts = (uint32_t*)ctx->h_counts.p;
-    uint32_t* pc = (uint32_t*)(ctx->h_counts.p + size_t(n_tiles) * 4);
-    HIP_CHECK(hipMemcpyAsync(tile_counts, ctx->d_results.p + L.r_tile_counts,
-                             size_t(n_tiles) * 4, hipMemcpyDeviceToHost,
-                             ctx->stream));
-    if (collect)
-        HIP_CHECK(hipMemcpyAsync(pc, ctx->d_results.p + L.r_cand_count, 4,
-                                 hipMemcpyDeviceToHost, ctx->stream));
-    if (do_aggs && ap.out_bytes) {
-        // aggregation results ride the same async batch + sync (a
-        // blocking copy after hit building cost ~40 us per split)
-        ctx->h_agg.ensure(ap.out_bytes + 64);
-        HIP_CHECK(hipMemcpyAsync(ctx->h_agg.p, ctx->d_results.p + L.r_agg,
-                                 ap.out_bytes, hipMemcpyDeviceToHost,
-                                 ctx->stream));
-    }
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const bool agg_out = do_aggs && ap.out_bytes;
     TileRun run;
+    uint32_t* tile_counts;
+    uint32_t* pc;
+    if (sel.onesync_wanted(collect)) {
+        // pass 0, the device pick + compaction and the inline survivors,
+        // then ONE download of everything up to the candidate records: tile
+        // counts | header | histogram | aggregation output are contiguous
+        sel.enqueue_onesync(sv.num_docs, tl.q.prune_k != 0);
+        const size_t head = agg_out ? L.r_agg + ap.out_bytes : L.r_agg;
+        ctx->h_counts.ensure(head + 64);
+        HIP_CHECK(hipMemcpyAsync(ctx->h_counts.p, ctx->d_results.p, head,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        tile_counts = (uint32_t*)(ctx->h_counts.p + L.r_tile_counts);
+        pc = (uint32_t*)(ctx->h_counts.p + L.r_cand_count);
+        run.agg_host = ctx->h_counts.p + L.r_agg;
+        sel.onesync_arrived(ctx->h_counts.p + L.r_cand_count,
+                            ctx->h_counts.p + L.r_hist);
+    } else {
+        if (collect && !sel.after) {
+            sel.enqueue_pass0(sv.num_docs);
+            sel.download_pass0();
+        }
+        // ---- download counts (into pinned staging: no pageable D2H)
+        ctx->h_counts.ensure(size_t(n_tiles) * 4 + 64);
+        tile_counts = (uint32_t*)ctx->h_counts.p;
+        pc = (uint32_t*)(ctx->h_counts.p + size_t(n_tiles) * 4);
+        HIP_CHECK(hipMemcpyAsync(tile_counts, ctx->d_results.p + L.r_tile_counts,
+                                 size_t(n_tiles) * 4, hipMemcpyDeviceToHost,
+                                 ctx->stream));
+        if (collect)
+            HIP_CHECK(hipMemcpyAsync(pc, ctx->d_results.p + L.r_cand_count, 4,
+                                     hipMemcpyDeviceToHost, ctx->stream));
+        if (do_aggs) ctx->h_agg.ensure(ap.out_bytes + 64);
+        if (agg_out) {
+            // aggregation results ride the same async batch + sync (a
+            // blocking copy after hit building cost ~40 us per split)
+            HIP_CHECK(hipMemcpyAsync(ctx->h_agg.p, ctx->d_results.p + L.r_agg,
+                                     ap.out_bytes, hipMemcpyDeviceToHost,
+                                     ctx->stream));
+        }
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        run.agg_host = ctx->h_agg.p;
+    }
     run.cand_n = collect ? *pc : 0;
     timer.mark("main+pass0+sync");
     float ms = 0;
@@ -3079,16 +3250,19 @@ static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
     timer.mark("assembly");
 
     uint64_t matched = sv.num_docs;  // pure match_all, no aggs: no kernel
+    const uint8_t* agg_host = nullptr;  // do_aggs always runs the kernel
     TopkSelector sel(ctx, sp.wide, sp.after != nullptr, leaf_max_hits);
     if (need_kernel) {
         qw_ensure_acct(ctx, ctx->d_scratch, L.scratch_bytes);
         qw_ensure_acct(ctx, ctx->d_results, L.results_bytes);
         sel.attach(L);
+        if (sel.onesync_wanted(collect)) sel.reserve_onesync(sv.num_docs);
         enqueue_uploads(ctx, L, ap, do_aggs);
         TileLaunch tl = fill_query_dev(ctx, ds, fq, sp, tt, ap, L, collect,
                                        do_aggs, leaf_max_hits, n_tiles);
         TileRun run = run_leaf_tile(ctx, sv, tl, L, ap, collect, do_aggs, sel, timer);
         matched = run.matched;
+        agg_host = run.agg_host;
         if (collect && run.cand_n > 0) {
             sel.band_n = run.cand_n;
             if (sp.after) sel.compact_cursor_band(cursor_ceil_key(sp, fq.scoring));
@@ -3108,8 +3282,7 @@ static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
 
     if (do_aggs) {
         // downloaded asynchronously with the counts batch (pinned)
-        ctx->h_agg.ensure(ap.out_bytes + 64);
-        decode_aggs(ap, L.r_agg, ctx->h_agg.p, matched, out.aggs);
+        decode_aggs(ap, L.r_agg, agg_host, matched, out.aggs);
         out.has_aggs = true;
     }
     timer.mark("aggs_assembly");
@@ -3296,6 +3469,9 @@ qw_ctx* qw_ctx_create(const char* config_json) {
             if (const mj::Value* tp = cfg->get("topk_prune"))
                 ctx->topk_prune = tp->kind == mj::Value::BOOL ? tp->b
                                                               : tp->as_i64() != 0;
+            if (const mj::Value* os = cfg->get("topk_onesync"))
+                ctx->topk_onesync = os->kind == mj::Value::BOOL ? os->b
+                                                                : os->as_i64() != 0;
         }
         return ctx;
     } catch (const std::exception& e) {
@@ -4046,6 +4222,15 @@ int32_t qw_topk_stats(qw_ctx* ctx, uint64_t out[4]) {
     out[1] = ctx->topk_unpruned;
     out[2] = ctx->topk_last_emitted;
     out[3] = ctx->topk_last_matched;
+    return QW_OK;
+}
+
+int32_t qw_topk_onesync_stats(qw_ctx* ctx, uint64_t out[4]) {
+    if (!ctx || !out) return QW_ERR_INVALID_ARGUMENT;
+    out[0] = ctx->topk_onesync_calls;
+    out[1] = ctx->topk_onesync_fallbacks;
+    out[2] = ctx->topk_onesync_last_survivors;
+    out[3] = ctx->topk_onesync_last_tail;
     return QW_OK;
 }
 
