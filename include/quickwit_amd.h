@@ -113,6 +113,12 @@ int32_t qw_merge_leaf_responses(const uint8_t* search_request_pb,
                                 const size_t* response_lens, size_t n,
                                 qw_buf* merged_out);
 
+/* Merge N intermediate aggregation blobs (QAGG1) of one aggregation request
+ * by key, as qw_merge_leaf_responses does for the blobs its responses carry;
+ * n == 1 decodes and re-encodes. Ctx-less, host-only. */
+int32_t qw_merge_intermediate_aggs(const uint8_t** blobs, const size_t* lens,
+                                   size_t n, qw_buf* merged_out);
+
 /* Finalize an intermediate aggregation blob (QAGG1) into the ES-shaped JSON
  * the reference's root returns for the same aggregation request. */
 int32_t qw_finalize_agg_to_json(const uint8_t* blob, size_t len,

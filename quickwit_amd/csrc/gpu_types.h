@@ -151,6 +151,35 @@ struct AggDev {
     uint64_t p_bound_off;
 };
 
+// percentiles under a terms aggregation: the second pass over the kept
+// buckets (k_terms_perc_sketch, kernels.hip). One launch per
+// percentiles sub.
+constexpr uint32_t TERMS_PERC_UNKEPT = 0xFFFFFFFFu;
+// dynamic LDS one block of the pass may use, boundary table and sketch
+// counters together. 64 KiB lets two such blocks share a CU's 160 KiB; the
+// effect of that occupancy on the pass has not been measured.
+constexpr uint32_t TERMS_PERC_LDS_BYTES = 64u * 1024u;
+struct TermsPercDev {
+    const uint8_t* split;     // device base of the split image
+    const uint32_t* bitmap;   // match set, tile-major u32 words (PRED_BITSET)
+    const uint32_t* remap;    // u32[cardinality]: kept slot or TERMS_PERC_UNKEPT
+    const double* bounds;     // f64[n_keys]: gamma^k, k = k_lo .. k_lo+n_keys-1
+    uint64_t* out;            // u64[kept * (n_keys + 1)], word 0 = zero bucket
+    uint32_t num_docs;
+    uint32_t cardinality;
+    uint32_t kept;
+    uint32_t n_keys;
+    uint64_t ord_off;         // terms ordinal column
+    uint64_t ord_nulls_off;   // 0 = non-nullable
+    uint64_t ord_offsets_off; // multi-valued: u32[num_docs+1] prefix; 0 = single
+    uint32_t ord_width;       // 1, 2 or 4
+    uint32_t val_kind;        // 0 = u64, 1 = i64/datetime, 2 = f64
+    uint64_t val_off;         // sub-aggregation value column (8 B values)
+    uint64_t val_nulls_off;   // 0 = non-nullable
+    uint32_t lds_bounds;      // 1 = boundary table staged in LDS
+    uint32_t lds_sketch;      // 1 = u32 counters in LDS, flushed at block end
+};
+
 struct QueryDev {
     const uint8_t* split;    // device base of the split image
     const uint8_t* scratch;  // device base of the query scratch (ranges etc.)

@@ -2015,4 +2015,95 @@ k_terms_union_bitmap(const uint8_t* split, uint64_t skip_off_tab_off,
     }
 }
 
+// ------------------------------------------- percentiles under terms, pass 2
+// One lane per document, grid-stride over 256-doc chunks. A matched doc whose
+// sub value is present finds the value's DDSketch slot (same search as
+// perc_slot over the same host doubles), then adds one to that slot of every
+// kept bucket among its term ordinals. LB stages the boundary table in LDS;
+// LS keeps the kept rows as u32 counters in LDS (a block sees fewer than 2^32
+// docs) and flushes the non-zero ones with one global atomic each. Dynamic
+// LDS: LB ? n_keys * 8 : 0 bytes, then LS ? kept * (n_keys + 1) * 4 : 0.
+template <bool LB, bool LS>
+__global__ void __launch_bounds__(256) k_terms_perc_sketch(TermsPercDev p) {
+    extern __shared__ uint64_t tp_lds[];
+    double* s_bounds = (double*)tp_lds;
+    uint32_t* s_cnt = (uint32_t*)(tp_lds + (LB ? p.n_keys : 0u));
+    const uint32_t row = p.n_keys + 1u;
+    const uint32_t n_cnt = p.kept * row;  // host caps the region at 2^25 words
+    if (LB)
+        for (uint32_t i = threadIdx.x; i < p.n_keys; i += blockDim.x)
+            s_bounds[i] = p.bounds[i];
+    if (LS)
+        for (uint32_t i = threadIdx.x; i < n_cnt; i += blockDim.x) s_cnt[i] = 0u;
+    if (LB || LS) __syncthreads();
+
+    const uint8_t* ocol = p.split + p.ord_off;
+    const uint64_t* onulls = (const uint64_t*)(p.split + p.ord_nulls_off);
+    const uint32_t* ooffs = (const uint32_t*)(p.split + p.ord_offsets_off);
+    const uint64_t* vcol = (const uint64_t*)(p.split + p.val_off);
+    const uint64_t* vnulls = (const uint64_t*)(p.split + p.val_nulls_off);
+    const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+    for (uint64_t d64 = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+         d64 < p.num_docs; d64 += stride) {
+        const uint32_t d = uint32_t(d64);
+        if (!((p.bitmap[d >> 5] >> (d & 31u)) & 1u)) continue;
+        if (p.val_nulls_off && !((vnulls[d >> 6] >> (d & 63u)) & 1ull)) continue;
+        if (p.ord_nulls_off && !((onulls[d >> 6] >> (d & 63u)) & 1ull)) continue;
+        const uint64_t raw = vcol[d];
+        const double v = p.val_kind == 2   ? __longlong_as_double(raw)
+                         : p.val_kind == 1 ? double(int64_t(raw))
+                                           : double(raw);
+        uint32_t sj = 0;
+        if (!(v < 1e-9)) {
+            uint32_t lo = 0, hi = p.n_keys - 1u;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                const double b = LB ? s_bounds[mid] : p.bounds[mid];
+                if (v <= b) hi = mid;
+                else lo = mid + 1u;
+            }
+            sj = lo + 1u;
+        }
+        uint32_t pos = d, end = d + 1u;
+        if (p.ord_offsets_off) {
+            pos = ooffs[d];
+            end = ooffs[d + 1u];
+        }
+        for (; pos < end; ++pos) {
+            const uint32_t ord = p.ord_width == 1   ? ocol[pos]
+                                 : p.ord_width == 2 ? ((const uint16_t*)ocol)[pos]
+                                                    : ((const uint32_t*)ocol)[pos];
+            if (ord >= p.cardinality) continue;
+            const uint32_t slot = p.remap[ord];
+            if (slot >= p.kept) continue;  // TERMS_PERC_UNKEPT
+            const uint32_t w = slot * row + sj;
+            if (LS) atomicAdd(&s_cnt[w], 1u);
+            else atomicAdd((unsigned long long*)p.out + w, 1ull);
+        }
+    }
+    if (LS) {
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < n_cnt; i += blockDim.x) {
+            const uint32_t c = s_cnt[i];
+            if (c) atomicAdd((unsigned long long*)p.out + i, (unsigned long long)c);
+        }
+    }
+}
+
+static void launch_terms_perc_sketch(const TermsPercDev& p, uint32_t grid,
+                                     uint32_t lds_bytes, hipStream_t stream) {
+    if (p.lds_bounds && p.lds_sketch)
+        hipLaunchKernelGGL((k_terms_perc_sketch<true, true>), dim3(grid),
+                           dim3(256), lds_bytes, stream, p);
+    else if (p.lds_bounds)
+        hipLaunchKernelGGL((k_terms_perc_sketch<true, false>), dim3(grid),
+                           dim3(256), lds_bytes, stream, p);
+    else if (p.lds_sketch)
+        hipLaunchKernelGGL((k_terms_perc_sketch<false, true>), dim3(grid),
+                           dim3(256), lds_bytes, stream, p);
+    else
+        hipLaunchKernelGGL((k_terms_perc_sketch<false, false>), dim3(grid),
+                           dim3(256), lds_bytes, stream, p);
+}
+
 }  // namespace qw

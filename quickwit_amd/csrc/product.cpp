@@ -1015,11 +1015,22 @@ static AggPlan plan_aggs(const SplitView& sv, const std::string& agg_json,
             }
         } else if (d.kind == AggDef::TERMS || d.kind == AggDef::CARDINALITY) {
             a.kind = AGGD_TERMS;
-            if (d.kind == AggDef::TERMS)
+            if (d.kind == AggDef::TERMS) {
+                // a percentiles sub has no value to order by: the refusal
+                // terms_order_sub_value would give at truncation, for every
+                // split and whatever its term count
+                std::string oname = d.order_target, ostat;
+                size_t dot = d.order_target.rfind('.');
+                if (dot != std::string::npos) {
+                    oname = d.order_target.substr(0, dot);
+                    ostat = d.order_target.substr(dot + 1);
+                }
                 for (auto& s : d.sub)
-                    if (s.kind == MetricAgg::PERCENTILES)
-                        throw std::runtime_error(
-                            "percentiles under terms (r1 limit)");
+                    if (s.kind == MetricAgg::PERCENTILES &&
+                        (s.name == oname || s.name == d.order_target))
+                        throw std::runtime_error("terms order: unknown stat '" +
+                                                 ostat + "'");
+            }
             if (f && f->type == FastFieldView::STR) {
                 a.n_buckets = f->cardinality;
                 a.values_off = f->values.off;
@@ -1034,6 +1045,23 @@ static AggPlan plan_aggs(const SplitView& sv, const std::string& agg_json,
                     for (size_t si = 0; si < d.sub.size(); ++si) {
                         const FastFieldView* sf =
                             sv.fast_field(d.sub[si].field);
+                        if (d.sub[si].kind == MetricAgg::PERCENTILES) {
+                            // sketched by the second pass over the kept
+                            // buckets (terms_perc_pass); here the slot stays
+                            // an empty stats slot, like a missing column
+                            if (sf && sf->type != FastFieldView::STR &&
+                                !sf->multi) {
+                                double mn, mx;
+                                col_min_max(*sf, &mn, &mx);
+                                if (mn < 0)
+                                    throw std::runtime_error(
+                                        "percentiles over negative values "
+                                        "(r1 limit)");
+                            }
+                            a.sub_values_off[si] = 0;
+                            a.sub_width[si] = 0;
+                            continue;
+                        }
                         if (sf && sf->type != FastFieldView::STR) {
                             a.sub_values_off[si] = sf->values.off;
                             a.sub_nulls_off[si] =
@@ -1059,6 +1087,14 @@ static AggPlan plan_aggs(const SplitView& sv, const std::string& agg_json,
                     throw std::runtime_error(
                         "terms aggregation over a numeric fast field on a "
                         ">2M-doc split (r1 limit)");
+                // numeric-keyed terms carry no sub-aggregations; a
+                // percentiles sub would render as nulls, so it stays refused
+                if (d.kind == AggDef::TERMS)
+                    for (auto& s : d.sub)
+                        if (s.kind == MetricAgg::PERCENTILES)
+                            throw std::runtime_error(
+                                "percentiles under terms over a numeric "
+                                "column (r1 limit)");
                 a.kind = AGGD_TERMS_NUM;
                 uint64_t want = uint64_t(sv.num_docs) * 2;
                 uint32_t slots = 1024;
@@ -3029,11 +3065,22 @@ struct AggOut {
     const uint64_t* counts() const { return (const uint64_t*)at(a.counts_out); }
 };
 
+static bool terms_has_perc_sub(const AggDef& d) {
+    if (d.kind != AggDef::TERMS) return false;
+    for (auto& s : d.sub)
+        if (s.kind == MetricAgg::PERCENTILES) return true;
+    return false;
+}
+
 static void decode_terms(const AggOut& o, const FastFieldView* f,
                          uint64_t matched, AggResult& r) {
     const AggDef& d = o.d;
     const AggDev& a = o.a;
     const uint64_t* counts = o.counts();
+    const bool perc_sub = terms_has_perc_sub(d);
+    if (perc_sub)
+        for (auto& s : d.sub)
+            r.sub_kinds.push_back(s.kind == MetricAgg::PERCENTILES ? 1 : 0);
     if (!a.n_buckets) return;
     if (a.nulls_off || a.offsets_off) {
         uint64_t m = 0;
@@ -3074,6 +3121,10 @@ static void decode_terms(const AggOut& o, const FastFieldView* f,
     if (d.kind == AggDef::TERMS)
         truncate_terms_split(r, effective_split_size(d.size, d.split_size),
                              d.order_target, d.order_asc, &d.sub);
+    // the kept rows, empty until terms_perc_pass fills them in this order
+    if (perc_sub)
+        r.term_sketches.assign(r.term_counts.size(),
+                               std::vector<SketchPayload>(d.sub.size()));
 }
 
 // decode packed 63-bit keys into the canonical per-source byte encoding
@@ -3191,6 +3242,139 @@ static void decode_aggs(const AggPlan& ap, size_t r_agg, const uint8_t* agg_out,
     }
 }
 
+// device buffers of one terms_perc_pass: the same holder as the gate
+// bitmaps, counted in hbm_used while they live and freed on whatever exit
+using PassBufs = GateBitmaps;
+
+// Percentiles under terms: the tile kernel counted every
+// ordinal and decode_terms cut the result to the kept terms; this second pass
+// sketches the sub values of those kept buckets only, over the match set of
+// the same plan (bitmap_eval: every predicate of pass 1, no search_after).
+static void terms_perc_pass(qw_ctx* ctx, const DeviceSplit& ds,
+                            const PlanNode& plan, const Schema& schema,
+                            const AggPlan& ap, uint64_t matched,
+                            IntermediateAggResults& out) {
+    const SplitView& sv = ds.view;
+    struct Sub {
+        size_t si;
+        const FastFieldView* sf;
+        int32_t k_lo;
+        std::vector<double> bounds;
+    };
+    for (size_t i = 0; i < ap.defs.size(); ++i) {
+        const AggDef& d = ap.defs[i];
+        const AggDev& a = ap.devs[i];
+        const FastFieldView* f = ap.fields[i];
+        AggResult& r = out.aggs[i];
+        if (!terms_has_perc_sub(d) || a.kind != AGGD_TERMS || !a.n_buckets)
+            continue;
+        const size_t kept = r.term_counts.size();
+        if (!kept || !matched) continue;
+
+        std::vector<Sub> subs;
+        for (size_t si = 0; si < d.sub.size(); ++si) {
+            if (d.sub[si].kind != MetricAgg::PERCENTILES) continue;
+            const FastFieldView* sf = sv.fast_field(d.sub[si].field);
+            // missing, str or multi-valued column: the sketches stay empty
+            if (!sf || sf->type == FastFieldView::STR || sf->multi) continue;
+            double mn, mx;
+            col_min_max(*sf, &mn, &mx);
+            int32_t k_lo = 0, k_hi = 0;
+            if (mx >= PERC_MIN_VALUE) {
+                k_lo = perc_key_for(std::max(mn, PERC_MIN_VALUE));
+                k_hi = perc_key_for(mx);
+            }
+            Sub s{si, sf, k_lo, {}};
+            if (uint64_t(kept) * (uint64_t(k_hi - k_lo + 1) + 1) > (1ull << 25))
+                throw std::runtime_error(
+                    "percentiles sketch region too large (r1 limit)");
+            perc_boundaries(k_lo, k_hi, s.bounds);
+            subs.push_back(std::move(s));
+        }
+        if (subs.empty()) continue;
+
+        const uint8_t* bm = bitmap_eval(ctx, ds, plan, schema);
+        PassBufs bufs(ctx);
+        // kept terms are in key order = ordinal order
+        std::vector<uint32_t> remap(f->cardinality, TERMS_PERC_UNKEPT);
+        for (size_t t = 0; t < kept; ++t) {
+            uint32_t ord = f->str_bound_ord(r.term_counts[t].first, false);
+            if (ord >= f->cardinality)
+                throw std::runtime_error("terms percentiles: kept term not in "
+                                         "the dictionary");
+            remap[ord] = uint32_t(t);
+        }
+        uint32_t* d_remap = (uint32_t*)bufs.alloc(remap.size() * 4);
+        HIP_CHECK(hipMemcpyAsync(d_remap, remap.data(), remap.size() * 4,
+                                 hipMemcpyHostToDevice, ctx->stream));
+        for (const Sub& s : subs) {
+            const uint32_t n_keys = uint32_t(s.bounds.size());
+            const size_t words = kept * (size_t(n_keys) + 1);
+            double* d_bounds = (double*)bufs.alloc(size_t(n_keys) * 8);
+            uint64_t* d_out = (uint64_t*)bufs.alloc(words * 8);
+            HIP_CHECK(hipMemcpyAsync(d_bounds, s.bounds.data(),
+                                     size_t(n_keys) * 8, hipMemcpyHostToDevice,
+                                     ctx->stream));
+            HIP_CHECK(hipMemsetAsync(d_out, 0, words * 8, ctx->stream));
+            TermsPercDev p{};
+            p.split = ds.d_image;
+            p.bitmap = (const uint32_t*)bm;
+            p.remap = d_remap;
+            p.bounds = d_bounds;
+            p.out = d_out;
+            p.num_docs = sv.num_docs;
+            p.cardinality = f->cardinality;
+            p.kept = uint32_t(kept);
+            p.n_keys = n_keys;
+            p.ord_off = a.values_off;
+            p.ord_nulls_off = a.nulls_off;
+            p.ord_offsets_off = a.offsets_off;
+            p.ord_width = a.value_width;
+            p.val_kind = s.sf->type == FastFieldView::U64   ? 0
+                         : s.sf->type == FastFieldView::F64 ? 2
+                                                            : 1;
+            p.val_off = s.sf->values.off;
+            p.val_nulls_off = s.sf->nullable ? s.sf->nulls.off : 0;
+            // LDS rule: the table when it fits half the
+            // block's budget, the counters when they fit what is left
+            size_t lds = 0;
+            if (size_t(n_keys) * 8 <= TERMS_PERC_LDS_BYTES / 2) {
+                p.lds_bounds = 1;
+                lds = size_t(n_keys) * 8;
+            }
+            if (lds + words * 4 <= TERMS_PERC_LDS_BYTES) {
+                p.lds_sketch = 1;
+                lds += words * 4;
+            }
+            // a block with LDS counters pays a zeroing and a flush of the
+            // whole region, so fewer, longer blocks: 512 = two for each of
+            // the MI355X's 256 CUs; without LDS counters 2048, as the other
+            // grid-stride kernels here use. Neither cap has been tuned.
+            uint32_t chunks = (sv.num_docs + 255u) / 256u;
+            uint32_t grid = std::min<uint32_t>(p.lds_sketch ? 512u : 2048u,
+                                               std::max<uint32_t>(chunks, 1u));
+            HIP_CHECK(hipEventRecord(ctx->ev_start, ctx->stream));
+            launch_terms_perc_sketch(p, grid, uint32_t(lds), ctx->stream);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipEventRecord(ctx->ev_stop, ctx->stream));
+            std::vector<uint64_t> host(words);
+            HIP_CHECK(hipMemcpyAsync(host.data(), d_out, words * 8,
+                                     hipMemcpyDeviceToHost, ctx->stream));
+            HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            float ms = 0;
+            HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+            record_kernel_time(ctx, "k_terms_perc_sketch", ms);
+            for (size_t t = 0; t < kept; ++t) {
+                const uint64_t* pw = host.data() + t * (size_t(n_keys) + 1);
+                SketchPayload& pp = r.term_sketches[t][s.si];
+                pp.zero = pw[0];
+                for (uint32_t j = 1; j <= n_keys; ++j)
+                    if (pw[j]) pp.counts[s.k_lo + int32_t(j) - 1] = pw[j];
+            }
+        }
+    }
+}
+
 static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
                                     const pb::SearchRequest& req, const Schema& schema) {
     SplitResult out;
@@ -3286,6 +3470,11 @@ static SplitResult search_split_gpu(qw_ctx* ctx, const DeviceSplit& ds,
         out.has_aggs = true;
     }
     timer.mark("aggs_assembly");
+    if (do_aggs) {
+        // last: its bitmap evaluation reuses the scratch and results buffers
+        terms_perc_pass(ctx, ds, plan, schema, ap, matched, out.aggs);
+        timer.mark("terms_perc_pass");
+    }
 
     out.micros = timer.micros();
     return out;
@@ -4088,6 +4277,25 @@ int32_t qw_merge_leaf_responses(const uint8_t* search_request_pb,
         m.partial_hits = std::move(all_hits);
         if (any_aggs) m.intermediate_aggregation_result = aggs.encode();
         fill_buf(merged_out, m.encode());
+        return QW_OK;
+    } catch (const std::exception& e) {
+        set_err(nullptr, e.what());
+        return QW_ERR_INTERNAL;
+    }
+}
+
+int32_t qw_merge_intermediate_aggs(const uint8_t** blobs, const size_t* lens,
+                                   size_t n, qw_buf* merged_out) {
+    using namespace qw;
+    try {
+        IntermediateAggResults aggs;
+        for (size_t i = 0; i < n; ++i) {
+            IntermediateAggResults ir =
+                IntermediateAggResults::decode(blobs[i], lens[i]);
+            if (i == 0) aggs = std::move(ir);
+            else aggs.merge(ir);
+        }
+        fill_buf(merged_out, aggs.encode());
         return QW_OK;
     } catch (const std::exception& e) {
         set_err(nullptr, e.what());

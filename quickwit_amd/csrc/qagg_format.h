@@ -16,7 +16,8 @@
 //     kind 5 (metric): 40 B stats (count,sum,min,max,sum_sq)
 //     kind 3 (terms/cardinality/composite): u8 key_kind, u64 matched,
 //        f64 error_bound, u32 ne; per entry: u16 key_len + key +
-//        u64 doc_count + n_sub x 40 B stats   (sorted by key bytes)
+//        u64 doc_count + per sub (sketch if sub_kind==1 else 40 B stats)
+//        (sorted by key bytes)
 //     else (1=date_histogram 2=histogram 4=range): u32 n_buckets; per
 //        bucket: f64 key + u64 doc_count + per sub (sketch if sub_kind==1
 //        else 40 B stats)   (sorted by key, sparse pre-merge)
@@ -136,6 +137,9 @@ struct AggResult {
     // per-term stats sub-aggs, parallel to term_counts (empty = no subs);
     // co-permuted by truncate_terms_split and key-merged with the counts
     std::vector<std::vector<StatsPayload>> term_subs;
+    // per-term percentiles sketches, parallel to term_subs (empty = no
+    // percentiles sub); entry [term][s] is used where sub_kinds[s] == 1
+    std::vector<std::vector<SketchPayload>> term_sketches;
     uint64_t terms_matched_docs = 0;
     // sum over truncated splits of the last-included term count — the ES
     // doc_count_error_upper_bound semantics the golden scenario pins
@@ -250,12 +254,16 @@ inline void truncate_terms_split(AggResult& r, int64_t split_size,
         std::sort(idx.begin(), idx.end());  // restore key order
         std::vector<std::pair<std::string, uint64_t>> tc;
         std::vector<std::vector<StatsPayload>> ts;
+        std::vector<std::vector<SketchPayload>> tk;
         for (size_t i : idx) {
             tc.push_back(std::move(r.term_counts[i]));
             if (!r.term_subs.empty()) ts.push_back(std::move(r.term_subs[i]));
+            if (!r.term_sketches.empty())
+                tk.push_back(std::move(r.term_sketches[i]));
         }
         r.term_counts = std::move(tc);
         r.term_subs = std::move(ts);
+        r.term_sketches = std::move(tk);
         return;
     }
     if (order_target == "_key") {
@@ -269,9 +277,14 @@ inline void truncate_terms_split(AggResult& r, int64_t split_size,
             if (!r.term_subs.empty())
                 r.term_subs.erase(r.term_subs.begin(),
                                   r.term_subs.begin() + drop);
+            if (!r.term_sketches.empty())
+                r.term_sketches.erase(r.term_sketches.begin(),
+                                      r.term_sketches.begin() + drop);
         } else {
             r.term_counts.resize(size_t(split_size));
             if (!r.term_subs.empty()) r.term_subs.resize(size_t(split_size));
+            if (!r.term_sketches.empty())
+                r.term_sketches.resize(size_t(split_size));
         }
         return;
     }
@@ -293,13 +306,17 @@ inline void truncate_terms_split(AggResult& r, int64_t split_size,
     std::sort(idx.begin(), idx.end());  // restore key order (indices ascend)
     std::vector<std::pair<std::string, uint64_t>> tc;
     std::vector<std::vector<StatsPayload>> ts;
+    std::vector<std::vector<SketchPayload>> tk;
     tc.reserve(idx.size());
     for (size_t i : idx) {
         tc.push_back(std::move(r.term_counts[i]));
         if (!r.term_subs.empty()) ts.push_back(std::move(r.term_subs[i]));
+        if (!r.term_sketches.empty())
+            tk.push_back(std::move(r.term_sketches[i]));
     }
     r.term_counts = std::move(tc);
     r.term_subs = std::move(ts);
+    r.term_sketches = std::move(tk);
 }
 
 inline int64_t effective_split_size(uint32_t size, int64_t split_size) {
@@ -361,6 +378,13 @@ struct IntermediateAggResults {
                     put(kv.first.data(), kl);
                     put(&kv.second, 8);
                     for (size_t s = 0; s < a.sub_names.size(); ++s) {
+                        if (s < a.sub_kinds.size() && a.sub_kinds[s] == 1) {
+                            put_sketch(ei < a.term_sketches.size() &&
+                                               s < a.term_sketches[ei].size()
+                                           ? a.term_sketches[ei][s]
+                                           : SketchPayload{});
+                            continue;
+                        }
                         StatsPayload sp;
                         if (ei < a.term_subs.size() &&
                             s < a.term_subs[ei].size())
@@ -462,6 +486,8 @@ struct IntermediateAggResults {
                 uint32_t ne;
                 get(&ne, 4);
                 a.term_counts.reserve(ne);
+                bool any_sketch = false;
+                for (uint8_t sk : a.sub_kinds) any_sketch |= sk == 1;
                 for (uint32_t e = 0; e < ne; ++e) {
                     uint16_t kl;
                     get(&kl, 2);
@@ -473,7 +499,14 @@ struct IntermediateAggResults {
                     a.term_counts.emplace_back(std::move(k), c);
                     if (!a.sub_names.empty()) {
                         std::vector<StatsPayload> subs(a.sub_names.size());
-                        for (auto& sp : subs) {
+                        std::vector<SketchPayload> sks(
+                            any_sketch ? a.sub_names.size() : 0);
+                        for (size_t s = 0; s < subs.size(); ++s) {
+                            if (a.sub_kinds[s] == 1) {
+                                get_sketch(sks[s]);
+                                continue;
+                            }
+                            StatsPayload& sp = subs[s];
                             get(&sp.count, 8);
                             get(&sp.sum, 8);
                             get(&sp.min, 8);
@@ -481,6 +514,8 @@ struct IntermediateAggResults {
                             get(&sp.sum_sq, 8);
                         }
                         a.term_subs.push_back(std::move(subs));
+                        if (any_sketch)
+                            a.term_sketches.push_back(std::move(sks));
                     }
                 }
             } else {
@@ -537,8 +572,17 @@ struct IntermediateAggResults {
                                ? r.term_subs[i]
                                : std::vector<StatsPayload>(r.sub_names.size());
                 };
+                // sketches ride along only when either side carries some
+                bool sks =
+                    !a.term_sketches.empty() || !b.term_sketches.empty();
+                auto sk_of = [](const AggResult& r, size_t i) {
+                    return i < r.term_sketches.size()
+                               ? r.term_sketches[i]
+                               : std::vector<SketchPayload>(r.sub_names.size());
+                };
                 std::vector<std::pair<std::string, uint64_t>> merged;
                 std::vector<std::vector<StatsPayload>> msubs;
+                std::vector<std::vector<SketchPayload>> msks;
                 merged.reserve(a.term_counts.size() + b.term_counts.size());
                 size_t x = 0, y = 0;
                 while (x < a.term_counts.size() || y < b.term_counts.size()) {
@@ -546,10 +590,12 @@ struct IntermediateAggResults {
                         (x < a.term_counts.size() &&
                          a.term_counts[x].first < b.term_counts[y].first)) {
                         if (subs) msubs.push_back(sub_of(a, x));
+                        if (sks) msks.push_back(sk_of(a, x));
                         merged.push_back(a.term_counts[x++]);
                     } else if (x >= a.term_counts.size() ||
                                b.term_counts[y].first < a.term_counts[x].first) {
                         if (subs) msubs.push_back(sub_of(b, y));
+                        if (sks) msks.push_back(sk_of(b, y));
                         merged.push_back(b.term_counts[y++]);
                     } else {
                         if (subs) {
@@ -558,6 +604,13 @@ struct IntermediateAggResults {
                             for (size_t s = 0; s < sb.size(); ++s)
                                 sa[s].merge(sb[s]);
                             msubs.push_back(std::move(sa));
+                        }
+                        if (sks) {
+                            auto ka = sk_of(a, x), kb = sk_of(b, y);
+                            ka.resize(std::max(ka.size(), kb.size()));
+                            for (size_t s = 0; s < kb.size(); ++s)
+                                ka[s].merge(kb[s]);
+                            msks.push_back(std::move(ka));
                         }
                         merged.emplace_back(a.term_counts[x].first,
                                             a.term_counts[x].second +
@@ -568,7 +621,9 @@ struct IntermediateAggResults {
                 }
                 a.term_counts = std::move(merged);
                 a.term_subs = std::move(msubs);
+                a.term_sketches = std::move(msks);
                 if (a.sub_names.empty()) a.sub_names = b.sub_names;
+                if (a.sub_kinds.empty()) a.sub_kinds = b.sub_kinds;
                 if (!a.key_kind) a.key_kind = b.key_kind;  // splits missing
                                                            // the column
                 a.terms_matched_docs += b.terms_matched_docs;
@@ -948,6 +1003,14 @@ inline std::string finalize_aggs_json(const IntermediateAggResults& ir,
                     o += ",";
                     mj::escape_to(o, d.sub[s].name);
                     o += ":";
+                    if (d.sub[s].kind == MetricAgg::PERCENTILES) {
+                        SketchPayload pp;
+                        if (b < a.term_sketches.size() &&
+                            s < a.term_sketches[b].size())
+                            pp = a.term_sketches[b][s];
+                        percentiles_to_json(o, d.sub[s], pp);
+                        continue;
+                    }
                     StatsPayload sp;
                     if (b < a.term_subs.size() && s < a.term_subs[b].size())
                         sp = a.term_subs[b][s];

@@ -15,7 +15,8 @@ Layout (little-endian), per qagg_format.h encode():
   kind 6 (percentiles): u64 zero, u32 ne, ne x (i32 k, u64 count)
   kind 5 (metric):      5 x 8B (count,sum,min,max,sum_sq)
   kind 3 (terms):       u8 key_kind, u64 matched, f64 error_bound, u32 ne,
-                        per entry: u16 klen + key + u64 count + n_sub x 40B
+                        per entry: u16 klen + key + u64 count +
+                        per sub (sketch if sub_kind==1 else 40B stats)
   else (1/2/4 buckets): u32 nb, per bucket: f64 key + u64 doc_count +
                         per sub (sketch if sub_kind==1 else 40B stats)
 """
@@ -76,7 +77,13 @@ def parse_blob(blob: bytes):
             off += 21
             for _i in range(ne):
                 (kl,) = struct.unpack_from("<H", blob, off)
-                off += 2 + kl + 8 + ns * STATS_SIZE
+                off += 2 + kl + 8
+                for sk in e.sub_kinds:
+                    if sk == 1:
+                        (ne2,) = struct.unpack_from("<I", blob, off + 8)
+                        off += 12 + ne2 * 12
+                    else:
+                        off += STATS_SIZE
         else:
             (nb,) = struct.unpack_from("<I", blob, off)
             off += 4
